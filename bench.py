@@ -2,8 +2,15 @@
 """bench.py -- Allreduce GB/s (device-resident, float32 SUM) of the MI355X-native
 fault-tolerant Allreduce.
 
-  python bench.py [--gpus 1] [--steps K] [--warmup W]
-  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+  python bench.py [--gpus 1] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ... [--full]
+
+A plain run does what its headline needs: set up, warm up, time the K steps, print the result
+line.  --full adds everything reported beside the headline (N = 1: live PMC traffic passes,
+the same-pair timing, the host-buffer e2e forms, the CPU baselines; N > 1: the side legs and
+every leg after the headline line).  --dump-outputs DIR writes what the last timed step
+returned to its caller as DIR/<name>.npy (float32; a fixed seeded sample of a large result);
+inputs are seeded, so two builds run with the same arguments can be compared array by array.
 
 N = 1: the single-GPU workload of BASELINE.json configs[1] -- the local-reduce HIP
        kernel (MPI_Reduce_local, the per-step bucket reduction) on two 256 MiB float32
@@ -214,6 +221,35 @@ def pmc_child(args):
     torch.cuda.synchronize()
 
 
+DUMP_MAX_ELEMS = 1 << 22     # --dump-outputs: at most 16 MiB of float32 per array
+
+
+def sample_for_dump(t):
+    """The array --dump-outputs writes for the result tensor `t`: all of it up to DUMP_MAX_ELEMS
+    elements, beyond that the elements at DUMP_MAX_ELEMS seeded positions (sorted, drawn with
+    replacement from a CPU generator: the same positions in every run and every build)."""
+    import torch
+    n = t.numel()
+    if n <= DUMP_MAX_ELEMS:
+        return t.detach().to("cpu", copy=True).numpy()
+    idx = torch.randint(0, n, (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(20240), dtype=torch.int64)
+    idx = idx.sort().values
+    return t.detach().index_select(0, idx.to(t.device)).cpu().numpy()
+
+
+def write_dump(outdir, arrays):
+    """DIR/<name>.npy per array (float32 / float64 as computed, integers as float64)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    names = {}
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        names[name] = {"file": name + ".npy", "dtype": str(a.dtype), "elements": int(a.size)}
+    return names
+
+
 def cpu_baseline_local_reduce(min_seconds=10.0, max_passes=2000):
     """The oracle's MPI_Reduce_local restatement on the host (1 thread), same workload."""
     import numpy as np
@@ -256,10 +292,13 @@ def c1_baseline(timeout=120.0):
 
 
 def single(args):
-    # the counter passes first, while this process has not opened the GPU (their child is a
-    # GPU process of its own)
+    # --full: the counter passes first, while this process has not opened the GPU (their child
+    # is a GPU process of its own)
     kname = "reduce_lds_kernel" if args.variant == 1 else "segment_kernel"
-    live_traffic, live_src = pmc_live(args, kname)
+    if args.full:
+        live_traffic, live_src = pmc_live(args, kname)
+    else:
+        live_traffic, live_src = None, {"measured_in_this_run": False, "skipped": "not --full"}
     import torch
     ftar = load_package()
     ftar.lib()
@@ -303,9 +342,9 @@ def single(args):
         k_ms = sum(e0.elapsed_time(e1) for e0, e1 in evs) / args.steps
     else:
         ms_step, k_ms = region(args.steps, args.pairs)
-    # the same launches on ONE pair (operands partly left in the Infinity Cache by the
-    # previous launch): what round 1 timed; reported, not the headline
-    _, k_same = region(min(args.steps, 100), 1)
+    if args.dump_outputs:
+        # what the last timed launch returned to its caller: the vector it reduced into
+        dumped = sample_for_dump(pairs[(args.steps - 1) % args.pairs][1])
     S = args.count * 4
     achieved = 3 * S / (k_ms * 1e-3) / 1e9
     if live_traffic:
@@ -328,19 +367,25 @@ def single(args):
                      "traffic_over_algorithmic": round(traffic / (3 * S), 5) if traffic else None,
                      "kernel": "reduce_lds_kernel<float,SUM>" if args.variant == 1 else "segment_kernel<float,SUM>",
                      "algorithmic_bytes_per_launch": 3 * S,
-                     "kernel_ms": round(k_ms, 4),
-                     "same_pair_kernel_ms": round(k_same, 4),
-                     "same_pair_GBps": round(3 * S / (k_same * 1e-3) / 1e9, 1)},
+                     "kernel_ms": round(k_ms, 4)},
     }
-    out["e2e"] = e2e_local(ftar, args.count, args.variant)
-    if args.no_cpu_baseline:
-        out["cpu_baseline"] = None
-    else:
-        out["cpu_baseline"] = cpu_baseline_local_reduce()
-        try:
-            out["cpu_baseline"]["c1"] = c1_baseline()
-        except Exception as e:  # reported, never fatal: the GPU line stands on its own
-            out["cpu_baseline"]["c1"] = {"error": str(e)[-300:]}
+    if args.full:
+        # the same launches on ONE pair (operands partly left in the Infinity Cache by the
+        # previous launch): what round 1 timed; reported, not the headline
+        _, k_same = region(min(args.steps, 100), 1)
+        out["roofline"].update({"same_pair_kernel_ms": round(k_same, 4),
+                                "same_pair_GBps": round(3 * S / (k_same * 1e-3) / 1e9, 1)})
+        out["e2e"] = e2e_local(ftar, args.count, args.variant)
+        if args.no_cpu_baseline:
+            out["cpu_baseline"] = None
+        else:
+            out["cpu_baseline"] = cpu_baseline_local_reduce()
+            try:
+                out["cpu_baseline"]["c1"] = c1_baseline()
+            except Exception as e:  # reported, never fatal: the GPU line stands on its own
+                out["cpu_baseline"]["c1"] = {"error": str(e)[-300:]}
+    if args.dump_outputs:
+        out["dumped_outputs"] = write_dump(args.dump_outputs, {"reduce_local_out": dumped})
     print(json.dumps(out), flush=True)
 
 
@@ -948,7 +993,10 @@ def multi(args):
     # torch is imported while rank 0 runs the side legs (the import opens no GPU device)
     imp = threading.Thread(target=lambda: importlib.import_module("torch"), daemon=True)
     imp.start()
-    cpu, c5, xgmi, side_info = side_legs(args, rank, world, devices, rehearsal)
+    if args.full:
+        cpu, c5, xgmi, side_info = side_legs(args, rank, world, devices, rehearsal)
+    else:
+        cpu = c5 = xgmi = side_info = None
     imp.join()
     import torch
     import torch.distributed as dist
@@ -1327,8 +1375,18 @@ def multi(args):
 
     line = build_line({}, None, 0.0)
     dog.line = line
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the Allreduce's result as the last timed call left it (the same vector on every rank)
+        dumped = line["dumped_outputs"] = write_dump(args.dump_outputs, {"allreduce_out": sample_for_dump(y)})
     if rank == 0:
         print(json.dumps(dict(line, line="headline")), flush=True)
+    if not args.full:  # the plain run ends with its headline
+        dist.barrier()
+        dog.done.set()
+        comm.finalize()
+        dist.destroy_process_group()
+        return
 
     # ---- optional legs: each runs only while the budget has room, records its own fate ----
     def opt_leg(name, est_s, fn):
@@ -1681,6 +1739,8 @@ def multi(args):
             world, S, rd_raw["t"], rd_raw["transport"], cal["single_link_GBps"] if cal and not rehearsal else None,
             rd_raw.get("t_direct"), rehearsal, rd_raw.get("breakdown"))
     line.update(final)
+    if dumped:
+        line["dumped_outputs"] = dumped
     line["c5_single_kill"] = c5
     line["legs"] = legs
     line["job_s"] = round(time.monotonic() - T_START, 1)
@@ -1719,6 +1779,12 @@ def main():
     ap.add_argument("--device", choices=["gpu", "cpu"], default="gpu", help=argparse.SUPPRESS)
     ap.add_argument("--no-pmc", action="store_true", help="N=1: skip the live rocprofv3 --pmc traffic passes")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: live PMC passes, same-pair timing, host-buffer e2e and CPU "
+                         "baselines (N=1); side legs and every leg after the headline line (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (float32; a fixed "
+                         "seeded sample of at most 16 MiB of a larger result)")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.pmc_child:

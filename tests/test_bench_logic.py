@@ -311,7 +311,7 @@ def test_rd_roofline_and_non_kernel_time():
     assert all(f is None or f <= 1.0 for f in _fracs(ns)), _fracs(ns)
 
 
-def _torchrun_cpu(tmp_path, extra_env, extra_args, timeout, nproc=2, count=65536):
+def _torchrun_cpu(tmp_path, extra_env, extra_args, timeout, nproc=2, count=65536, full=True):
     import socket
     import subprocess
     import sys
@@ -324,7 +324,8 @@ def _torchrun_cpu(tmp_path, extra_env, extra_args, timeout, nproc=2, count=65536
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--device",
-           "cpu", "--dist-backend", "gloo", "--count", str(count), "--steps", "3", "--warmup", "1"] + extra_args
+           "cpu", "--dist-backend", "gloo", "--count", str(count), "--steps", "3", "--warmup", "1"] + extra_args + \
+        (["--full"] if full else [])
     t0 = time.monotonic()
     cp = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
     subprocess.run(f"rm -f /dev/shm/ftarhs-bench{os.getpid()}-*", shell=True)
@@ -338,9 +339,12 @@ def test_bench_multi_headline_survives_hung_and_failing_legs(hostsim, tmp_path):
     host-sim library: the configs[4] side leg hangs past its deadline, one transport and the
     RD leg fail.  The headline line is printed right after configs[3] is timed, with the
     contract's keys and the north-star block; the final line completes with every leg's
-    fate recorded, inside the budgets."""
+    fate recorded, inside the budgets.  The side budget is 40 s: the CPU baseline leg gets a fifth
+    of it (bench.py side_legs), 8 s for a no-op make and three 2-rank host jobs that take 0.1 s
+    on an idle host -- room for a host where starting a process costs a hundred times that."""
+    side_budget = 40
     cp, lines, took = _torchrun_cpu(tmp_path, {"FTAR_BENCH_HANG": "c5", "FTAR_BENCH_FAIL": "transports:direct,rd"},
-                                    ["--side-budget", "20", "--c5-draws", "1"], 200)
+                                    ["--side-budget", str(side_budget), "--c5-draws", "1"], 200)
     assert cp.returncode == 0, cp.stderr[-3000:]
     assert [d["line"] for d in lines] == ["headline", "final"], cp.stdout[-2000:]
     head, fin = lines
@@ -353,14 +357,14 @@ def test_bench_multi_headline_survives_hung_and_failing_legs(hostsim, tmp_path):
         assert ns["target"] and ns["priced"]["survey_153.6_assumed"]["survey_t_roof_ms"] > 0 and "met" in ns
     assert head["value"] == fin["value"]
     assert fin["side_legs"]["c5"]["status"] == "timeout" and "killed" in fin["c5_single_kill"]["error"]
-    assert fin["side_legs"]["total_s"] <= 20 + 2
+    assert fin["side_legs"]["total_s"] <= side_budget + 2
     assert fin["transports"]["direct"]["error"].startswith("transports:direct: forced failure")
     assert fin["transports"]["relay2hop"]["raben_ms"] > 0
     assert fin["legs"]["rd"]["status"] == "error" and fin["rd"] is None
     assert "non_kernel_ms" in fin["north_star"] and fin["north_star"]["kernels_ms"] >= 0
     assert fin["exact_on_node"]["all_exact"], fin["exact_on_node"]
     assert fin["int32_rank_checksum_ok"] == {"raben": True, "rd": True}
-    assert fin["cpu_baseline"]["value"] and fin["cpu_baseline"]["cores"] == 2
+    assert fin["cpu_baseline"]["value"] and fin["cpu_baseline"]["cores"] == 2, (fin["cpu_baseline"], fin["side_legs"])
     # what the run decides (analysis/analyze.py decisions), in the line itself
     nd = fin["node_decisions"]
     assert "error" not in nd, nd
@@ -369,6 +373,29 @@ def test_bench_multi_headline_survives_hung_and_failing_legs(hostsim, tmp_path):
     sweep = fin["size_sweep_us"]
     assert sweep[str(8 * 65536)]["raben_us"] > 0 and sweep[str(8 * 65536)]["rd_us"] > 0, sweep
     assert took < 150, took
+
+
+@pytest.mark.timeout(120)
+def test_bench_multi_plain_run_ends_with_its_headline(hostsim, tmp_path):
+    """Without --full the N > 1 run times configs[3], prints the headline line and ends: no side
+    legs, none of the later legs.  --dump-outputs writes rank 0's result vector -- 65536 + 5
+    elements, below the dump's cap, so all of it: the sum of the two ranks' seeded inputs, bit for
+    bit (two addends: one IEEE add whatever the schedule)."""
+    import numpy as np
+    import torch
+    n = 65536 + 5
+    cp, lines, took = _torchrun_cpu(tmp_path, {}, ["--dump-outputs", str(tmp_path / "out")], 100, count=n, full=False)
+    assert cp.returncode == 0, cp.stderr[-3000:]
+    assert [d["line"] for d in lines] == ["headline"], cp.stdout[-2000:]
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "north_star"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["value"] > 0 and d["side_legs"] is None and d["cpu_baseline"] is None
+    assert "legs" not in d and "exact_on_node" not in d
+    got = np.load(tmp_path / "out" / "allreduce_out.npy")
+    assert got.dtype == np.float32 and got.shape == (n,)
+    xs = [torch.rand(n, generator=torch.Generator().manual_seed(1000 + r)) * 2 - 1 for r in range(2)]
+    assert np.array_equal(got, (xs[0] + xs[1]).numpy())
 
 
 @pytest.mark.timeout(240)

@@ -1,7 +1,8 @@
 """bench.py's two paths as the driver runs them, on the one-GPU test box.
 
-N = 1: `python bench.py` -- one JSON line with the contract's keys, the roofline of the
-local-reduce kernel and the CPU baselines.
+N = 1: `python bench.py --full` -- one JSON line with the contract's keys, the roofline of the
+local-reduce kernel and the CPU baselines; the plain run -- the headline keys alone, and the
+last timed launch's result written by --dump-outputs.
 N = 2: the path the driver's 8-GPU SCALE run takes (torchrun, one rank per GPU, ftar_init's
 torchrun bootstrap, every leg of the N > 1 line), rehearsed with both ranks on GPU 0
 (FTAR_DEVICE=0) and gloo for torch.distributed (RCCL refuses two ranks on one device),
@@ -31,7 +32,7 @@ def _last_json(out):
 def test_bench_single_gpu_line():
     # --no-pmc: the live counter passes (two rocprofv3 runs of a child) are the default bench's,
     # checked on the box by tools/gpu_check.sh's bench step; here the fallback's label is checked
-    cp = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2",
+    cp = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--full",
                          "--no-cpu-baseline", "--no-pmc"], capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert cp.returncode == 0, cp.stderr[-2000:]
     d = _last_json(cp.stdout)
@@ -50,6 +51,54 @@ def test_bench_single_gpu_line():
     assert "rotating" in d["config"]["buffers"]
 
 
+EXPECTED_DUMP = r'''
+import sys
+import numpy as np
+import torch
+count, pairs, steps, warmup = map(int, sys.argv[1:5])
+g = torch.Generator(device="cuda").manual_seed(42)
+ps = [(torch.rand(count, device="cuda", generator=g) * 2 - 1, torch.rand(count, device="cuda", generator=g) * 2 - 1)
+      for _ in range(pairs)]
+for k in list(range(warmup)) + list(range(steps)):
+    x, y = ps[k % pairs]
+    y += x
+idx = torch.randint(0, count, (1 << 22,), generator=torch.Generator().manual_seed(20240), dtype=torch.int64)
+np.save(sys.argv[5], ps[(steps - 1) % pairs][1].cpu()[idx.sort().values].numpy())
+'''
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times its steps and prints the headline keys only; --dump-outputs
+    writes the vector the last timed launch reduced into.  8 M + 3 elements: beyond the dump's
+    4 Mi-element cap, so the seeded sample is what is compared, and no multiple of the kernel's
+    tile.  Inputs are seeded: a second process recomputes the expected values from the same seed
+    -- warm-up and timed launches add x into y once each, pair after pair (one float32 add per
+    element and launch, in launch order) -- and the dump equals them bit for bit."""
+    import numpy as np
+    count, pairs, steps, warmup = (8 << 20) + 3, 2, 5, 2
+    cp = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                         "--warmup", str(warmup), "--count", str(count), "--pairs", str(pairs), "--dump-outputs",
+                         str(tmp_path / "out")], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert cp.returncode == 0, cp.stderr[-2000:]
+    d = _last_json(cp.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "roofline"):
+        assert k in d, k
+    assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0
+    for k in ("e2e", "cpu_baseline"):  # --full's
+        assert k not in d, k
+    assert "same_pair_kernel_ms" not in d["roofline"]
+    assert d["roofline"]["traffic_source"]["live"]["skipped"] == "not --full"
+    assert d["dumped_outputs"]["reduce_local_out"]["elements"] == 1 << 22
+    got = np.load(tmp_path / "out" / "reduce_local_out.npy")
+    assert got.dtype == np.float32 and got.shape == (1 << 22,)
+    # the same inputs, the same launches, on torch (a child: this process opens no GPU, conftest.py)
+    cp = subprocess.run([sys.executable, "-c", EXPECTED_DUMP, str(count), str(pairs), str(steps), str(warmup),
+                         str(tmp_path / "want.npy")], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert cp.returncode == 0, cp.stderr[-2000:]
+    want = np.load(tmp_path / "want.npy")
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
 @pytest.mark.timeout(600)
 def test_bench_two_rank_scale_path():
     with socket.socket() as s:
@@ -61,7 +110,7 @@ def test_bench_two_rank_scale_path():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2",
            "--dist-backend", "gloo", "--no-variants", "--count", str(1 << 20), "--steps", "2", "--warmup", "1",
-           "--c5-draws", "3"]
+           "--c5-draws", "3", "--full"]
     cp = subprocess.run(cmd, capture_output=True, text=True, timeout=540, cwd=ROOT, env=env)
     assert cp.returncode == 0, cp.stderr[-3000:]
     lines = [json.loads(l) for l in cp.stdout.splitlines() if l.startswith("{")]

@@ -77,18 +77,22 @@ def test_launcher_never_a_kill_candidate(hostsim):
     """run_mpi.sh passes the rank program through FTAR_PROG, so the reference killer's
     rule (run/kill_procs.sh:12: R-state processes whose command line contains "main")
     matches the rank processes but never `timeout` or the ftrun launcher, which sleeps in
-    sigtimedwait.  Sampled over a 2 s stretched run of a 4-rank job."""
+    sigtimedwait.  Sampled over a 2 s stretched run of a 4-rank job; a failure says how many
+    samples were taken and what they showed."""
     import time
     exe = os.path.join(ROOT, "tests", "hostsim", "_build", "src", "raben", "main")
     env = dict(os.environ, FTAR_PROG=exe, FTAR_LOOP_SECONDS="2", FTAR_HOSTSIM_TAG=f"kc{os.getpid()}")
     proc = subprocess.Popen(["timeout", "30", os.path.join(ROOT, "tests", "hostsim", "_build", "bin", "ftrun"),
                              "-np", "4", "50000"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     seen_ranks, launchers, bad = set(), set(), set()
+    samples, states = [], set()  # when each listing came back; (state, program) of the job's processes
     try:
         t0 = time.time()
         while proc.poll() is None and time.time() - t0 < 20:
             rows = []
-            for line in subprocess.run(["ps", "-e", "-o", "pid=,ppid=,stat=,args="], capture_output=True,
+            # -ww: whole command lines, whatever COLUMNS or a terminal on stdin says (cut at the
+            # width, a long checkout path loses the "main" the rule looks for)
+            for line in subprocess.run(["ps", "-e", "-ww", "-o", "pid=,ppid=,stat=,args="], capture_output=True,
                                        text=True).stdout.splitlines():
                 f = line.split(None, 3)
                 if len(f) == 4:
@@ -104,10 +108,12 @@ def test_launcher_never_a_kill_candidate(hostsim):
             for pid, ppid, st, args in rows:
                 if pid not in tree:
                     continue
+                states.add((st, os.path.basename(args.split()[0])))
                 if ppid == proc.pid:
                     launchers.add(pid)
                 if "main" in args and st.startswith("R"):  # the reference killer's candidates
                     (bad if pid == proc.pid or ppid == proc.pid else seen_ranks).add(pid)
+            samples.append(round(time.time() - t0, 2))
             time.sleep(0.02)
         out, err = proc.communicate(timeout=30)
     finally:
@@ -117,7 +123,7 @@ def test_launcher_never_a_kill_candidate(hostsim):
     assert proc.returncode == 0, err[-2000:]
     assert launchers, "launcher never observed"
     assert not bad, (bad, launchers)
-    assert seen_ranks, "no rank process was ever a candidate"
+    assert seen_ranks, ("no rank process was ever a candidate", len(samples), samples[:5], sorted(states))
     assert out.count("Hello from") == 4
 
 

@@ -29,10 +29,23 @@ HS = os.path.join(ROOT, "tests", "hostsim")
 OUT = "_build_o3"
 
 
+def _march() -> str:
+    """x86-64-v3 where the building host itself has it (AVX2, BMI2, FMA), plain x86-64 elsewhere:
+    a host without AVX2 must still be able to run the baseline it built."""
+    try:
+        for line in open("/proc/cpuinfo"):
+            if line.startswith("flags"):
+                return "x86-64-v3" if {"avx2", "bmi2", "fma", "movbe"} <= set(line.split(":", 1)[1].split()) \
+                    else "x86-64"
+    except OSError:
+        pass
+    return "x86-64"
+
+
 def build():
     # x86-64-v3 (AVX2), not -march=native: the binaries are built here and run on the GPU
     # box's host CPU, a different microarchitecture
-    subprocess.run(["make", "-s", "-C", HS, f"OUT={OUT}", "CFLAGS=-O3 -march=x86-64-v3 -g -std=c11 -Wall "
+    subprocess.run(["make", "-s", "-C", HS, f"OUT={OUT}", f"CFLAGS=-O3 -march={_march()} -g -std=c11 -Wall "
                     "-Wno-unused-parameter -fPIC -D_GNU_SOURCE", f"{OUT}/src/rd/main", f"{OUT}/src/raben/main",
                     f"{OUT}/bin/ftrun"], check=True)
 

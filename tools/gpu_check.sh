@@ -6,7 +6,7 @@
 #   smoke      __graft_entry__.smoke()
 #   pytest     the whole -m gpu suite (heartbeat file under $OUT for long cases); PYTEST_PATHS
 #              narrows it (test ids, space-separated), PYTEST_ARGS adds options (no spaces inside one)
-#   bench      bench.py N = 1 (rotating buffers) and its register-kernel variant
+#   bench      bench.py --full, N = 1 (rotating buffers) and its register-kernel variant
 #   prof       rocprofv3 kernel trace + stats of bench.py N = 1
 #   pmc        one rocprofv3 --pmc pass per counter (FETCH_SIZE, WRITE_SIZE) of bench.py
 #   hbmsweep   tools/hbm_sweep.hip: C2 variants and calibration streams, rotating buffers
@@ -44,9 +44,9 @@ if has pytest; then
   rc=$?; tail -6 "$OUT/pytest_gpu.log"; stop_on_fault $rc pytest
 fi
 if has bench; then
-  timeout -k 10 300 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 300 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
   rc=$?; cat "$OUT/bench.json"; stop_on_fault $rc bench
-  timeout -k 10 300 python bench.py --variant 0 --no-cpu-baseline > "$OUT/bench_v0.json" 2>> "$OUT/bench.err"
+  timeout -k 10 300 python bench.py --full --variant 0 --no-cpu-baseline > "$OUT/bench_v0.json" 2>> "$OUT/bench.err"
   rc=$?; cat "$OUT/bench_v0.json"; stop_on_fault $rc bench_v0
 fi
 if has prof; then
@@ -79,7 +79,7 @@ if has rehearse || has rehearse8; then
   for n in $ns; do
     FTAR_DEVICE=0 FTAR_C5_RANKS=${C5_RANKS:-5} timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
         --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --gpus $n --steps ${REH_STEPS:-5} \
-        --warmup 1 --dist-backend gloo > "$OUT/rehearse_$n.json" 2> "$OUT/rehearse_$n.err" &
+        --warmup 1 --dist-backend gloo --full > "$OUT/rehearse_$n.json" 2> "$OUT/rehearse_$n.err" &
     pid=$!
     while kill -0 $pid 2>/dev/null; do sleep 30; echo "rehearse_$n running $(date +%T)"; done
     wait $pid; rc=$?; tail -c 600 "$OUT/rehearse_$n.json"; tail -3 "$OUT/rehearse_$n.err"; stop_on_fault $rc rehearse_$n
