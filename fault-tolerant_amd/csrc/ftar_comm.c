@@ -10,6 +10,7 @@
 #endif
 #include "ftar_internal.h"
 
+#include <math.h>
 #include <signal.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -133,6 +134,14 @@ void ftar_maybe_die(ftar_comm *c, int phase, int step, int point)
     }
 }
 
+void ftar_pass_post(ftar_comm *c)
+{
+    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BEFORE);
+    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_DURING);
+    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_AFTER);
+    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BARRIER);
+}
+
 int ftar_set_kills(ftar_comm *c, const ftar_kill *kills, int nkills)
 {
     if (!c || nkills < 0 || nkills > FTAR_MAX_KILLS) return FTAR_ERR_ARG;
@@ -144,17 +153,76 @@ int ftar_set_kills(ftar_comm *c, const ftar_kill *kills, int nkills)
 
 /* ---- bootstrap ------------------------------------------------------------ */
 
-/* The comm's environment defaults: every value must be a whole number (or a decimal where
- * `real`) inside [lo, hi] -- "auto", "on", "" or "1x" are refused with FTAR_ERR_ARG and a
- * message naming the variable, never read as 0 the way atoi would.  The same
- * ranges ftar_comm_set_option accepts. */
-struct env_knob {
-    const char *name;
+/* The comm's knobs, one row each: ftar_init_rank reads the environment by it, and
+ * ftar_comm_set_option / ftar_comm_get_option find the option's field in it.
+ *
+ * In the environment every value must be a whole number (or a decimal where `real`) inside
+ * [lo, hi] -- "auto", "on", "" or "1x" are refused with FTAR_ERR_ARG and a message naming the
+ * variable, never read as 0 the way atoi would.  ftar_comm_set_option is laxer
+ * where it always was: any finite v >= 0, a switch normalised to v != 0, a level saturating
+ * at hi, a size or a time stored as given; only a K_INT keeps the row's range. */
+enum { K_BOOL, K_INT, K_LEVEL, K_SIZE, K_SECONDS, K_USECONDS };
+enum { NO_OPT = -1, MiB = 1 << 20 }; /* (sizes: up to 2^62) */
+#define KNOB(name, opt, lo, hi, dflt, real, kind, field) {name, opt, lo, hi, dflt, real, kind, offsetof(ftar_comm, field)}
+static const struct knob {
+    const char *name; /* in the environment */
+    int opt;          /* ftar_option, or NO_OPT */
     double lo, hi, dflt;
-    int real;
+    int real; /* a decimal, else a whole number */
+    int kind; /* of the field: int (K_BOOL, K_INT, K_LEVEL), size_t, double seconds (K_USECONDS: given in us) */
+    size_t off;
+} knobs[] = {
+    KNOB("FTAR_VERBOSE", NO_OPT, 0, 9, 0, 0, K_INT, verbose),
+    KNOB("FTAR_LOOP_SECONDS", FTAR_OPT_LOOP_SECONDS, 0, 1e6, 0, 1, K_SECONDS, loop_seconds),
+    KNOB("FTAR_OVERLAP", FTAR_OPT_OVERLAP, 0, 1, 1, 0, K_BOOL, overlap),
+    KNOB("FTAR_RELAY", FTAR_OPT_RELAY, 0, 1, 1, 0, K_BOOL, relay),
+    KNOB("FTAR_REDUNDANCY", FTAR_OPT_REDUNDANCY, 0, 2, 2, 0, K_INT, redundancy),
+    KNOB("FTAR_COPY_ENGINE", FTAR_OPT_COPY_ENGINE, 0, 1, 0, 0, K_BOOL, copy_engine),
+    KNOB("FTAR_MESH", FTAR_OPT_MESH, 0, 1, 1, 0, K_BOOL, mesh),
+    KNOB("FTAR_PUSH", FTAR_OPT_PUSH, 0, 2, 0, 0, K_LEVEL, push),
+    KNOB("FTAR_MESH_WAIT", FTAR_OPT_MESH_WAIT, 0, 1, 1, 0, K_BOOL, mesh_wait),
+    KNOB("FTAR_GATE", FTAR_OPT_GATE, 0, 1, 1, 0, K_BOOL, gate),
+    KNOB("FTAR_GATE_HOLD_US", NO_OPT, 0, 1e12, 2000, 1, K_USECONDS, gate_hold_s),
+    KNOB("FTAR_GATE_MAX", FTAR_OPT_GATE_MAX, 0, 0x1p62, MiB, 0, K_SIZE, gate_max),
+    KNOB("FTAR_ONESHOT_MAX", FTAR_OPT_ONESHOT_MAX, 0, 0x1p62, MiB, 0, K_SIZE, oneshot_max),
+    KNOB("FTAR_EXPORT", NO_OPT, 0, 1, 1, 0, K_BOOL, export_user),
+    KNOB("FTAR_STAGE_MAX", NO_OPT, 0, 0x1p62, MiB, 0, K_SIZE, stage_max),
+    KNOB("FTAR_HOST_PIPE", NO_OPT, 0, 1, 1, 0, K_BOOL, host_pipe),
+    KNOB("FTAR_RELAY_MIN", FTAR_OPT_RELAY_MIN, 0, 0x1p62, 4 * MiB, 0, K_SIZE, relay_min),
 };
+#undef KNOB
+#define NKNOBS (sizeof(knobs) / sizeof(knobs[0]))
 
-static int env_value(int rank, const struct env_knob *k, double *out)
+static void knob_store(ftar_comm *c, const struct knob *k, double v)
+{
+    void *f = (char *)c + k->off;
+    switch (k->kind) {
+    case K_SIZE: *(size_t *)f = (size_t)v; break;
+    case K_SECONDS: *(double *)f = v; break;
+    case K_USECONDS: *(double *)f = v * 1e-6; break;
+    default: *(int *)f = (int)v;
+    }
+}
+
+static double knob_load(const ftar_comm *c, const struct knob *k) /* in the unit knob_store takes */
+{
+    const void *f = (const char *)c + k->off;
+    switch (k->kind) {
+    case K_SIZE: return (double)*(const size_t *)f;
+    case K_SECONDS: return *(const double *)f;
+    case K_USECONDS: return *(const double *)f * 1e6;
+    default: return *(const int *)f;
+    }
+}
+
+static const struct knob *knob_of(ftar_option opt)
+{
+    for (size_t i = 0; i < NKNOBS && (int)opt != NO_OPT; i++)
+        if (knobs[i].opt == (int)opt) return &knobs[i];
+    return NULL;
+}
+
+static int env_value(int rank, const struct knob *k, double *out)
 {
     const char *e = getenv(k->name);
     *out = k->dflt;
@@ -179,41 +247,14 @@ int ftar_init_rank(ftar_comm **out, const char *job, int rank, int size, int dev
     c->wrank = rank;
     c->wsize = size;
     c->device = device;
-    const double MiB = (double)(1 << 20), SZ = 4611686018427387904.0; /* sizes up to 2^62 */
-    const struct env_knob knobs[] = {
-        {"FTAR_VERBOSE", 0, 9, 0, 0},         {"FTAR_LOOP_SECONDS", 0, 1e6, 0, 1},
-        {"FTAR_OVERLAP", 0, 1, 1, 0},         {"FTAR_RELAY", 0, 1, 1, 0},
-        {"FTAR_REDUNDANCY", 0, 2, 2, 0},      {"FTAR_COPY_ENGINE", 0, 1, 0, 0},
-        {"FTAR_MESH", 0, 1, 1, 0},            {"FTAR_PUSH", 0, 2, 0, 0},
-        {"FTAR_MESH_WAIT", 0, 1, 1, 0},       {"FTAR_GATE", 0, 1, 1, 0},
-        {"FTAR_GATE_HOLD_US", 0, 1e12, 2000, 1}, {"FTAR_GATE_MAX", 0, SZ, MiB, 0},
-        {"FTAR_ONESHOT_MAX", 0, SZ, MiB, 0},  {"FTAR_EXPORT", 0, 1, 1, 0},
-        {"FTAR_STAGE_MAX", 0, SZ, MiB, 0},    {"FTAR_HOST_PIPE", 0, 1, 1, 0},
-        {"FTAR_RELAY_MIN", 0, SZ, 4 * MiB, 0},
-    };
-    double v[sizeof(knobs) / sizeof(knobs[0])];
-    for (size_t i = 0; i < sizeof(knobs) / sizeof(knobs[0]); i++)
-        if (env_value(rank, &knobs[i], &v[i])) {
+    for (size_t i = 0; i < NKNOBS; i++) {
+        double v;
+        if (env_value(rank, &knobs[i], &v)) {
             free(c);
             return FTAR_ERR_ARG;
         }
-    c->verbose = (int)v[0];
-    c->loop_seconds = v[1];
-    c->overlap = (int)v[2];
-    c->relay = (int)v[3];
-    c->redundancy = (int)v[4];
-    c->copy_engine = (int)v[5];
-    c->mesh = (int)v[6];
-    c->push = (int)v[7];
-    c->mesh_wait = (int)v[8];
-    c->gate = (int)v[9];
-    c->gate_hold_s = v[10] * 1e-6;
-    c->gate_max = (size_t)v[11];
-    c->oneshot_max = (size_t)v[12];
-    c->export_user = (int)v[13];
-    c->stage_max = (size_t)v[14];
-    c->host_pipe = (int)v[15];
-    c->relay_min = (size_t)v[16];
+        knob_store(c, &knobs[i], v);
+    }
     int create = getenv("FTAR_LAUNCHER") == NULL;
     int rc = ftar_ctrl_attach(&c->job, job, rank, size, create);
     if (rc) {
@@ -566,54 +607,30 @@ int ftar_comm_set_stream(ftar_comm *c, void *stream)
 
 int ftar_comm_set_option(ftar_comm *c, ftar_option opt, double v)
 {
-    if (!c || v < 0) return FTAR_ERR_ARG;
-    switch (opt) {
-    case FTAR_OPT_OVERLAP: c->overlap = v != 0; break;
-    case FTAR_OPT_RELAY: c->relay = v != 0; break;
-    case FTAR_OPT_RELAY_MIN: c->relay_min = (size_t)v; break;
-    case FTAR_OPT_LOOP_SECONDS: c->loop_seconds = v; break;
-    case FTAR_OPT_COPY_ENGINE: c->copy_engine = v != 0; break;
-    case FTAR_OPT_REDUNDANCY:
-        if (v != 0 && v != 1 && v != 2) return FTAR_ERR_ARG;
-        c->redundancy = (int)v;
-        break;
-    case FTAR_OPT_MESH: c->mesh = v != 0; break;
-    case FTAR_OPT_ONESHOT_MAX: c->oneshot_max = (size_t)v; break;
-    case FTAR_OPT_PUSH: c->push = v >= 2 ? 2 : v != 0; break;
-    case FTAR_OPT_MESH_WAIT: c->mesh_wait = v != 0; break;
-    case FTAR_OPT_GATE: c->gate = v != 0; break;
-    case FTAR_OPT_GATE_MAX: c->gate_max = (size_t)v; break;
-    case FTAR_OPT_FLAG_SYNC:
-        if (fdev_set_knob(c->dev, FDEV_KNOB_FLAG_SYNC, v != 0)) return FTAR_ERR_ARG;
-        break;
-    case FTAR_OPT_TREE_UNROLL:
-        if (v != (int)v || fdev_set_knob(c->dev, FDEV_KNOB_TREE_UNROLL, (int)v)) return FTAR_ERR_ARG;
-        break;
-    default: return FTAR_ERR_ARG;
-    }
+    if (!c || !(v >= 0) || isinf(v)) return FTAR_ERR_ARG; /* negative, NaN or infinite */
+    /* the device layer's own two */
+    if (opt == FTAR_OPT_FLAG_SYNC) return fdev_set_knob(c->dev, FDEV_KNOB_FLAG_SYNC, v != 0) ? FTAR_ERR_ARG : FTAR_SUCCESS;
+    if (opt == FTAR_OPT_TREE_UNROLL)
+        return v > 4 || v != (int)v || fdev_set_knob(c->dev, FDEV_KNOB_TREE_UNROLL, (int)v) ? FTAR_ERR_ARG : FTAR_SUCCESS;
+    const struct knob *k = knob_of(opt);
+    if (!k) return FTAR_ERR_ARG;
+    if (k->kind == K_BOOL) v = v != 0;
+    if (k->kind == K_LEVEL) v = v >= k->hi ? k->hi : v != 0;
+    if (k->kind == K_INT && (v > k->hi || v != (int)v)) return FTAR_ERR_ARG;
+    knob_store(c, k, v);
     return FTAR_SUCCESS;
 }
 
 int ftar_comm_get_option(const ftar_comm *c, ftar_option opt, double *v)
 {
     if (!c || !v) return FTAR_ERR_ARG;
-    switch (opt) {
-    case FTAR_OPT_OVERLAP: *v = c->overlap; break;
-    case FTAR_OPT_RELAY: *v = c->relay; break;
-    case FTAR_OPT_RELAY_MIN: *v = (double)c->relay_min; break;
-    case FTAR_OPT_LOOP_SECONDS: *v = c->loop_seconds; break;
-    case FTAR_OPT_COPY_ENGINE: *v = c->copy_engine; break;
-    case FTAR_OPT_REDUNDANCY: *v = c->redundancy; break;
-    case FTAR_OPT_MESH: *v = c->mesh; break;
-    case FTAR_OPT_ONESHOT_MAX: *v = (double)c->oneshot_max; break;
-    case FTAR_OPT_PUSH: *v = c->push; break;
-    case FTAR_OPT_MESH_WAIT: *v = c->mesh_wait; break;
-    case FTAR_OPT_GATE: *v = c->gate; break;
-    case FTAR_OPT_GATE_MAX: *v = (double)c->gate_max; break;
-    case FTAR_OPT_FLAG_SYNC: *v = fdev_get_knob(c->dev, FDEV_KNOB_FLAG_SYNC); break;
-    case FTAR_OPT_TREE_UNROLL: *v = fdev_get_knob(c->dev, FDEV_KNOB_TREE_UNROLL); break;
-    default: return FTAR_ERR_ARG;
+    if (opt == FTAR_OPT_FLAG_SYNC || opt == FTAR_OPT_TREE_UNROLL) {
+        *v = fdev_get_knob(c->dev, opt == FTAR_OPT_FLAG_SYNC ? FDEV_KNOB_FLAG_SYNC : FDEV_KNOB_TREE_UNROLL);
+        return FTAR_SUCCESS;
     }
+    const struct knob *k = knob_of(opt);
+    if (!k) return FTAR_ERR_ARG;
+    *v = knob_load(c, k);
     return FTAR_SUCCESS;
 }
 
@@ -795,10 +812,7 @@ int ftar_prelaunch(ftar_comm *c, int dtype, int op, const fdev_seg *segs, int ns
     int gated = 0;
     c->gplan.valid = 0;
     if (!c->gate || nseg <= 0 || nseg > FDEV_MAX_SEGS) return 0;
-    if (fdev_run_gated(c->dev, dtype, op, segs, nseg, tag, stage_dst, stage_src, stage_n, &gated)) {
-        fprintf(stderr, "ftar: rank %d: launch failed: %s\n", c->wrank, fdev_last_error());
-        ftar_ctrl_abort(&c->job, FTAR_ERR_DEVICE);
-    }
+    ftar_launch_check(c, fdev_run_gated(c->dev, dtype, op, segs, nseg, tag, stage_dst, stage_src, stage_n, &gated));
     if (!gated) return 0;
     c->gplan = (struct ftar_gplan){1, dtype, op, tag, nseg, {{0}}};
     memcpy(c->gplan.segs, segs, sizeof(fdev_seg) * (size_t)nseg);
@@ -839,11 +853,24 @@ void ftar_host_copy_failed(ftar_comm *c, const char *what)
     ftar_ctrl_abort(&c->job, FTAR_ERR_DEVICE);
 }
 
-int ftar_drain(ftar_comm *c)
+/* A launch returned rc: a failure ends the job (MPI_Abort), as a device error in a drain does. */
+int ftar_launch_check(ftar_comm *c, int rc)
+{
+    if (rc) {
+        fprintf(stderr, "ftar: rank %d: launch failed: %s\n", c->wrank, fdev_last_error());
+        ftar_ctrl_abort(&c->job, FTAR_ERR_DEVICE);
+    }
+    return rc;
+}
+
+/* The drains' one body: wait for a stream with `sync` (fdev_sync / fdev_sync_bg), polling
+ * `poll(arg)` meanwhile; the main stream's drains also clear the slot's in-flight word. */
+static int drain(ftar_comm *c, int (*sync)(ftar_dev *, int (*)(void *), void *), int (*poll)(void *), void *arg,
+                 int clear_inflight)
 {
     double t0 = now_s();
-    int rc = fdev_sync(c->dev, ftar_ctrl_poll, &c->job);
-    if (!rc) atomic_store_explicit(&c->job.shm->slot[c->wrank].inflight, 0, memory_order_release);
+    int rc = sync(c->dev, poll, arg);
+    if (!rc && clear_inflight) atomic_store_explicit(&c->job.shm->slot[c->wrank].inflight, 0, memory_order_release);
     c->stats.drain_s += now_s() - t0;
     if (rc) {
         fprintf(stderr, "ftar: rank %d: device error: %s\n", c->wrank, fdev_last_error());
@@ -851,6 +878,8 @@ int ftar_drain(ftar_comm *c)
     }
     return rc;
 }
+
+int ftar_drain(ftar_comm *c) { return drain(c, fdev_sync, ftar_ctrl_poll, &c->job, 1); }
 
 void *ftar_flag(ftar_comm *c, int w)
 {
@@ -874,51 +903,21 @@ int ftar_watch_peers(void *arg)
     return 0;
 }
 
-int ftar_drain_watch(ftar_comm *c)
-{
-    double t0 = now_s();
-    int rc = fdev_sync(c->dev, ftar_watch_peers, c);
-    if (!rc) atomic_store_explicit(&c->job.shm->slot[c->wrank].inflight, 0, memory_order_release);
-    c->stats.drain_s += now_s() - t0;
-    if (rc) {
-        fprintf(stderr, "ftar: rank %d: device error: %s\n", c->wrank, fdev_last_error());
-        ftar_ctrl_abort(&c->job, FTAR_ERR_DEVICE);
-    }
-    return rc;
-}
+int ftar_drain_watch(ftar_comm *c) { return drain(c, fdev_sync, ftar_watch_peers, c, 1); }
 
-int ftar_drain_bg(ftar_comm *c)
-{
-    double t0 = now_s();
-    int rc = fdev_sync_bg(c->dev, ftar_ctrl_poll, &c->job);
-    c->stats.drain_s += now_s() - t0;
-    if (rc) {
-        fprintf(stderr, "ftar: rank %d: device error: %s\n", c->wrank, fdev_last_error());
-        ftar_ctrl_abort(&c->job, FTAR_ERR_DEVICE);
-    }
-    return rc;
-}
+/* the background stream: the main stream's launches stay in flight */
+int ftar_drain_bg(ftar_comm *c) { return drain(c, fdev_sync_bg, ftar_ctrl_poll, &c->job, 0); }
 
 int ftar_run_bg(ftar_comm *c, int dtype, int op, const fdev_seg *segs, int nseg, int tag)
 {
     note_segs(c, dtype, segs, nseg);
-    int rc = fdev_run_bg(c->dev, dtype, op, segs, nseg, tag);
-    if (rc) {
-        fprintf(stderr, "ftar: rank %d: launch failed: %s\n", c->wrank, fdev_last_error());
-        ftar_ctrl_abort(&c->job, FTAR_ERR_DEVICE);
-    }
-    return rc;
+    return ftar_launch_check(c, fdev_run_bg(c->dev, dtype, op, segs, nseg, tag));
 }
 
 int ftar_run(ftar_comm *c, int dtype, int op, const fdev_seg *segs, int nseg, int tag)
 {
     note_segs(c, dtype, segs, nseg);
-    int rc = fdev_run(c->dev, dtype, op, segs, nseg, tag);
-    if (rc) {
-        fprintf(stderr, "ftar: rank %d: launch failed: %s\n", c->wrank, fdev_last_error());
-        ftar_ctrl_abort(&c->job, FTAR_ERR_DEVICE);
-    }
-    return rc;
+    return ftar_launch_check(c, fdev_run(c->dev, dtype, op, segs, nseg, tag));
 }
 
 void ftar_regroup(ftar_comm *c, int dead, int repl)
@@ -961,10 +960,7 @@ int ftar_single_rank(ftar_comm *c, const void *sbuf, void *rbuf, size_t bytes)
     ftar_exchange_done(c);
     ftar_maybe_die(c, FTAR_PH_PRE, 0, FTAR_PT_AFTER);
     ftar_maybe_die(c, FTAR_PH_PRE, 0, FTAR_PT_BARRIER);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BEFORE);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_DURING);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_AFTER);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BARRIER);
+    ftar_pass_post(c);
     ftar_sync_fatal(c);
     ftar_stats_end(c);
     return FTAR_SUCCESS;

@@ -169,6 +169,8 @@ void ftar_sync_fatal(ftar_comm *c);
 /* drain the device stream (busy wait, abort-aware) */
 void ftar_host_copy_failed(ftar_comm *c, const char *what); /* aborts the job */
 int ftar_drain(ftar_comm *c);
+/* every launch's status goes through here: rc != 0 is reported and aborts the job */
+int ftar_launch_check(ftar_comm *c, int rc);
 /* enqueue one segment kernel */
 int ftar_run(ftar_comm *c, int dtype, int op, const fdev_seg *segs, int nseg, int tag);
 /* Queue a step's segment launch ahead of the barrier that readies its operands, behind a
@@ -206,6 +208,9 @@ int ftar_single_rank(ftar_comm *c, const void *sbuf, void *rbuf, size_t bytes);
 
 /* deterministic fault injection at (phase, step, point) */
 void ftar_maybe_die(ftar_comm *c, int phase, int step, int point);
+/* the four kill points of FTAR_PH_POST, before a call's closing agree: BEFORE, DURING, AFTER,
+ * BARRIER, in that order */
+void ftar_pass_post(ftar_comm *c);
 
 /* remove `dead` (comm rank), moving the entry at comm rank `repl` into its place */
 void ftar_regroup(ftar_comm *c, int dead, int repl);

@@ -28,53 +28,21 @@
  * not in sbuf/tmp, so a second impersonation by the same rank stays correct; a
  * recovery that needs redundancy a replacement rank never received aborts instead of
  * replaying garbage; new_entry pulls only the dead rank's live window.
+ *
+ * This file: the entry points, the step-by-step schedule and the two error handlers.  The
+ * one-hop mesh forms (power-of-two p without a spare) are in ftar_raben_mesh.c, included
+ * below the handlers; the context and helpers both use are in ftar_raben.h.
  */
-#include "ftar_internal.h"
+#include "ftar_raben.h"
 
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
-#include <unistd.h>
 
-#define MAXSTEPS 32
 /* host-buffer pipeline: vectors of at least HOST_PIPE_MIN bytes go through in chunks of
  * HOST_PIPE_CHUNK bytes (at most HOST_PIPE_MAX chunks, FDEV_MAX_CHUNKS) */
 #define HOST_PIPE_MIN ((size_t)16 << 20)
 #define HOST_PIPE_CHUNK ((size_t)8 << 20)
 #define HOST_PIPE_MAX 16
-
-typedef struct {
-    ftar_comm *c;
-    int dtype, op;
-    size_t es, count;
-    int steps, adjsize, rem;
-    int rank, vrank, corr, has_recov;
-    int keep_recov; /* step 0 also pulls the partner's other half into T (recovery data) */
-    int alt;        /* RS accumulators alternate W / T (an idle spare at the call's start; rb_acc) */
-    int bg_pending; /* step-0 redundancy copy still running on the background stream */
-    int fast_io;    /* power of two, no recovery data: sbuf/rbuf used in place (see below) */
-    int out_done;   /* the last allgather step already stored this rank's result in rbuf */
-    int mesh;       /* fast_io on the full mesh: one-hop reduce-scatter and allgather */
-    int push;       /* the mesh's reduce-scatter by remote stores into the owners' R (FTAR_OPT_PUSH) */
-    int64_t slot;   /* push: elements per source slot in an owner's R */
-    int oneshot;    /* mesh of a small vector: every block in its owner's tree, one launch */
-    int own_in_rbuf; /* the mesh's tree stored this rank's final block in rbuf too: the allgather skips it */
-    int io_safe;     /* sbuf == rbuf or the two do not overlap: rbuf may be written while peers read sbuf */
-    int devwait;     /* the mesh's allgather ordered behind the peers' trees on the device (rb_mesh_devwait) */
-    /* the one-shot launch queued ahead of the barrier (rb_oneshot_prelaunch): its plan, to
-     * be checked against the one the inputs' resolution gives */
-    int gated;
-    struct rb_batch {
-        const void *src[FDEV_MAX_BATCH * FDEV_MAX_BATCH];
-        void *out[FDEV_MAX_BATCH];
-        size_t n[FDEV_MAX_BATCH];
-        unsigned remote[FDEV_MAX_BATCH];
-    } gplan;
-    int in0_w[FTAR_MAX_RANKS]; /* world rank whose IN held vrank v's input at RS step 0 */
-    int64_t rindex[MAXSTEPS], sindex[MAXSTEPS], rcount[MAXSTEPS], scount[MAXSTEPS];
-} rb_ctx;
-
-static int rb_real(const rb_ctx *x, int v) { return (v < x->rem) ? v * 2 : v + x->rem; }
 
 static void rb_vrank(rb_ctx *x)
 {
@@ -82,35 +50,6 @@ static void rb_vrank(rb_ctx *x)
     if (x->rank < 2 * x->rem) x->vrank = (x->rank % 2 == 0) ? x->rank / 2 : -1;
     else x->vrank = x->rank - x->rem;
 }
-
-/* Windows of virtual rank v at every step (raben/rabenseifner.c:170-249).  The
- * reference compares real ranks (rank < dest); the vrank->rank map is monotone, so
- * that is bit s of v being 0. */
-static void rb_windows(int v, size_t count, int steps, int64_t *rindex, int64_t *sindex, int64_t *rcount,
-                       int64_t *scount)
-{
-    int64_t wsize = (int64_t)count;
-    rindex[0] = sindex[0] = 0;
-    for (int s = 0; s < steps; s++) {
-        int lower = !((v >> s) & 1);
-        if (lower) {
-            rcount[s] = wsize / 2;
-            scount[s] = wsize - rcount[s];
-            sindex[s] = rindex[s] + rcount[s];
-        } else {
-            scount[s] = wsize / 2;
-            rcount[s] = wsize - scount[s];
-            rindex[s] = sindex[s] + scount[s];
-        }
-        if (s + 1 < steps) {
-            rindex[s + 1] = rindex[s];
-            sindex[s + 1] = rindex[s];
-            wsize = rcount[s];
-        }
-    }
-}
-
-static void *at(const rb_ctx *x, void *base, int64_t idx) { return (char *)base + (size_t)idx * x->es; }
 
 /* The buffer holding every rank's reduce-scatter window after step s (uniform: the same on
  * every rank and for the whole call).  Without a spare, W: every failure aborts, and the
@@ -322,469 +261,16 @@ static void rb_handler_ag(rb_ctx *x, uint64_t newf, int fs)
     c->stats.recoveries++;
 }
 
-/* Push form of the mesh (FTAR_OPT_PUSH): where the pull form's tree kernel reads the p - 1
- * peers' parts of this rank's block over xGMI, here every rank stores its part of each
- * peer's block INTO that peer (the owner's R, one slot per source) and each owner reduces
- * its block from local memory.  Link bytes are the same (S/p per link and direction); the
- * fabric moves remote stores instead of remote loads, which bench.py compares on the node.
- * Slot j of owner u holds x_(u^j) over u's final block -- the tree's src[j] -- starting at
- * the same element offset modulo 16 bytes as the block itself, so the copies and the tree
- * keep their 16-byte vector bodies.  Returns the slot stride in elements, or 0 if the p - 1
- * slots do not fit the workspace (the caller then pulls). */
-static int64_t rb_push_slot(const rb_ctx *x)
+/* the mesh forms: rb_push_slot, rb_oneshot_prelaunch, rb_oneshot, rb_mesh */
+#include "ftar_raben_mesh.c"
+
+/* The call's context: its arguments checked (the reference's errors) and the form it takes,
+ * decided from the comm's options, p and the size alone, so the same on every rank.  Decides
+ * only -- nothing is launched, staged or published here. */
+static int rb_select_form(rb_ctx *x, const void *sbuf, void *rbuf, size_t count, ftar_dtype dtype, ftar_op op,
+                          ftar_comm *c)
 {
-    int64_t e16 = (int64_t)(16 / x->es), bmax = 0;
-    for (int u = 0; u < x->adjsize; u++) {
-        int64_t ri[MAXSTEPS], si[MAXSTEPS], rc[MAXSTEPS], sc[MAXSTEPS];
-        rb_windows(u, x->count, x->steps, ri, si, rc, sc);
-        if (rc[x->steps - 1] > bmax) bmax = rc[x->steps - 1];
-    }
-    int64_t stride = (bmax + e16 + 63) / 64 * 64; /* 256-byte multiples (x 4 or 8 B) */
-    if ((size_t)((x->adjsize - 1) * stride) * x->es > x->c->ws_bytes) return 0;
-    return stride;
-}
-
-static void *rb_push_at(const rb_ctx *x, void *R, int j, int64_t block_off)
-{
-    int64_t e16 = (int64_t)(16 / x->es);
-    return at(x, R, (int64_t)(j - 1) * x->slot + block_off % e16);
-}
-
-/* The reduce-scatter of rb_mesh in push form (see rb_push_slot): one launch of p - 1 remote
- * copies, the phase's agree (every slot has landed), the owner's tree over local memory,
- * and one more agree before the allgather reads the owners' blocks.  Kill points and
- * outcomes are rb_mesh's (no idle rank: every failure aborts). */
-static void rb_mesh_push_rs(rb_ctx *x, const void *sbuf, void *rbuf)
-{
-    ftar_comm *c = x->c;
-    const int L = x->steps, p = x->adjsize, v = x->vrank;
-    void *W = c->ws[WS_W];
-    int64_t own0 = x->rindex[L - 1], own_n = x->rcount[L - 1];
-    for (int s = 0; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_BEFORE);
-    ftar_enter(c);
-    fdev_seg segs[FDEV_MAX_SEGS];
-    int ns = 0;
-    for (int j = 1; j < p; j++) { /* owner u = v ^ j: its tree takes x_v as src[j] */
-        int u = v ^ j;
-        int64_t ri[MAXSTEPS], si[MAXSTEPS], rc[MAXSTEPS], sc[MAXSTEPS];
-        rb_windows(u, x->count, L, ri, si, rc, sc);
-        void *R = ftar_buf(c, c->order[rb_real(x, u)], WS_R);
-        segs[ns++] = (fdev_seg){FDEV_COPY, FDEV_REMOTE_OUT, rb_push_at(x, R, j, ri[L - 1]),
-                                at(x, (void *)sbuf, ri[L - 1]), NULL, (size_t)rc[L - 1], NULL};
-    }
-    double lb0 = ftar_link_bytes(c);
-    ftar_run(c, x->dtype, x->op, segs, ns, FDEV_TAG_STEP0);
-    ftar_launched(c, FTAR_PH_LOOP, 0); /* every step's DURING point: the pushes are in flight */
-    for (int s = 1; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_DURING);
-    ftar_drain(c);
-    ftar_exchange_done(c);
-    c->stats.step0_link_bytes += ftar_link_bytes(c) - lb0;
-    c->stats.steps += L;
-    c->stats.mesh_steps++;
-    for (int s = 0; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_AFTER);
-    for (int s = 0; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_BARRIER);
-    uint64_t newf = ftar_step_sync(c, 3); /* every slot landed (:258-265) */
-    if (newf) rb_handler_rs(x, newf, L - 1); /* no idle rank: aborts */
-    const void *src[FDEV_MAX_TREE];
-    src[0] = at(x, (void *)sbuf, own0);
-    for (int j = 1; j < p; j++) src[j] = rb_push_at(x, c->ws[WS_R], j, own0);
-    /* push == 2: the allgather rides on the tree -- its result goes to this rank's rbuf
-     * and straight into every peer's W (the owner's block, remote stores) */
-    void *more[FDEV_MAX_TREE];
-    int nmore = 0;
-    if (x->push == 2) {
-        for (int s = L - 1; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_BEFORE);
-        ftar_enter(c);
-        for (int j = 1; j < p; j++) more[nmore++] = at(x, ftar_buf(c, c->order[rb_real(x, v ^ j)], WS_W), own0);
-    }
-    void *out = x->push == 2 ? at(x, rbuf, own0) : at(x, W, own0);
-    if (x->push == 1) { /* as the pull form: the block into rbuf too, where co-aligned (rb_mesh) */
-        more[0] = at(x, rbuf, own0);
-        x->own_in_rbuf = x->io_safe && (((uintptr_t)more[0] ^ (uintptr_t)out) & 15) == 0;
-        nmore = x->own_in_rbuf;
-    }
-    if (fdev_tree_out(c->dev, x->dtype, x->op, src, p, 0, out, more, nmore, x->push == 2, (size_t)own_n,
-                      FDEV_TAG_STEP)) {
-        fprintf(stderr, "ftar: rank %d: launch failed: %s\n", c->wrank, fdev_last_error());
-        ftar_ctrl_abort(&c->job, FTAR_ERR_DEVICE);
-    }
-    ftar_note_launch(c, x->push == 2 ? more[0] : NULL, 0);
-    if (x->push == 2) {
-        ftar_launched(c, FTAR_PH_AG, L - 1);
-        for (int s = L - 2; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_DURING);
-    }
-    ftar_drain(c);
-    if (x->push == 2) {
-        ftar_exchange_done(c);
-        c->stats.steps += L;
-        c->stats.mesh_steps++;
-        for (int s = L - 1; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_AFTER);
-        for (int s = L - 1; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_BARRIER);
-    }
-    /* every owner's block is final (push == 1: before the allgather pulls it; push == 2:
-     * every peer's pushed block has landed in this rank's W) */
-    newf = ftar_step_sync(c, 3);
-    if (newf) rb_handler_rs(x, newf, L - 1);
-}
-
-/* push == 2, after rb_mesh_push_rs: the peers' blocks, pushed into this rank's W, to rbuf
- * (one local copy launch), then the ERRORS_ARE_FATAL barrier (:357-360).  The copy comes
- * before this rank arrives at the barrier: no peer's next call can push into W while it
- * is being read. */
-static int rb_mesh_push_finish(rb_ctx *x, void *rbuf)
-{
-    ftar_comm *c = x->c;
-    const int L = x->steps, p = x->adjsize, v = x->vrank;
-    fdev_seg segs[FDEV_MAX_SEGS];
-    int ns = 0;
-    for (int j = 1; j < p; j++) {
-        int64_t ri[MAXSTEPS], si[MAXSTEPS], rc[MAXSTEPS], sc[MAXSTEPS];
-        rb_windows(v ^ j, x->count, L, ri, si, rc, sc);
-        segs[ns++] = (fdev_seg){FDEV_COPY, 0, at(x, rbuf, ri[L - 1]), at(x, c->ws[WS_W], ri[L - 1]), NULL,
-                                (size_t)rc[L - 1], NULL};
-    }
-    ftar_run(c, x->dtype, x->op, segs, ns, FDEV_TAG_LOCAL);
-    ftar_drain(c);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BEFORE);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_DURING);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_AFTER);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BARRIER);
-    uint64_t newf = ftar_step_sync(c, 3);
-    if (newf) rb_handler_ag(x, newf, 0); /* no idle rank: aborts */
-    ftar_stats_end(c);
-    return FTAR_SUCCESS;
-}
-
-/* The tolerant region at power-of-two p without an idle rank, on the full xGMI mesh.
- *
- * Recursive halving leaves in vrank v's final block the value
- *     T(v, L),  T(v, 0) = x_v,  T(v, s+1) = T(v, s) op T(v ^ 2^s, s)
- * (raben/rabenseifner.c:231-237: own window first, the partner's second; the partner's
- * window was reduced by the same rule).  With the sources listed owner-relative
- * (src[j] = x_{v^j}) that is the left-to-right balanced tree over j, which one tree
- * kernel computes from p - 1 one-hop pulls -- every link of the GPU busy with 1/p of the
- * vector instead of one link per step.  The allgather (:299-355) likewise pulls every
- * peer's final block straight into rbuf.  Per rank and direction each link carries
- * S/p for the reduce-scatter and S/p for the allgather: the mesh lower bound for an
- * allreduce, half of what a 2-hop relay moves.
- *
- * The reference's per-step states are unobservable here: with no idle rank every
- * handler aborts (new_entry = -1, raben/errhandler.c:207-211, 377-378), so a failure
- * anywhere in a phase ends the job exactly as it would at that step's agree.  Every
- * step's kill points are still passed (the injected death lands in the same phase), and
- * each phase ends in the reference's agree + barrier. */
-/* The mesh allgather's one launch: this rank's final block W -> rbuf and every peer's final
- * block, pulled out of its W, into rbuf (the operands are known before the reduce-scatter's
- * barrier: the launch can be queued ahead of it, behind a gate). */
-static int rb_mesh_ag_segs(rb_ctx *x, void *rbuf, fdev_seg *segs)
-{
-    ftar_comm *c = x->c;
-    const int L = x->steps, p = x->adjsize, v = x->vrank;
-    int ns = 0;
-    if (!x->own_in_rbuf)
-        segs[ns++] = (fdev_seg){FDEV_COPY, 0, at(x, rbuf, x->rindex[L - 1]), at(x, c->ws[WS_W], x->rindex[L - 1]),
-                                NULL, (size_t)x->rcount[L - 1], NULL};
-    for (int j = 1; j < p; j++) {
-        int u = v ^ j;
-        int64_t ri[MAXSTEPS], si[MAXSTEPS], rc[MAXSTEPS], sc[MAXSTEPS];
-        rb_windows(u, x->count, L, ri, si, rc, sc);
-        void *PW = ftar_buf(c, c->order[rb_real(x, u)], WS_W);
-        segs[ns++] = (fdev_seg){FDEV_COPY, FDEV_REMOTE_X, at(x, rbuf, ri[L - 1]), at(x, PW, ri[L - 1]), NULL,
-                                (size_t)rc[L - 1], NULL};
-    }
-    return ns;
-}
-
-/* The mesh with its allgather ordered on the device (FTAR_OPT_MESH_WAIT), continuing
- * rb_mesh after the tree launch.  The reduce-scatter's agree only ever served to say "every
- * owner's block is final" -- with no idle rank every failure aborts the job at whichever
- * agree sees it (new_entry = -1, raben/errhandler.c:207-211, 377-378) -- so that fact moves
- * to the device: each rank releases its tree (a fenced marker) and publishes the call's token
- * in its line of the control block's flag page (host memory every GPU maps); the allgather,
- * queued right behind, runs once every peer's flag holds the token.  Per call this saves one
- * host agree round, one drain and the allgather's launch latency; the call keeps its first
- * and last agree.  A peer that dies before publishing: the drain's failure detector gives
- * the wait up (the allgather returns untouched), and the last agree sees the death -- the
- * handler aborts, as at the agree this form leaves out.  A wait the device gave up with
- * every member alive (its timeout): each rank publishes its verdict in the last agree round,
- * so all of them learn it alike; by then every tree is released (each rank drained its own
- * before arriving), the ranks whose allgather returned untouched launch it again (it never
- * writes what it reads), and one more round keeps the peers' next call off their W until it
- * is done.  Every step's kill points are passed, in the order both launches are queued: RS
- * BEFORE, DURING; AG BEFORE, DURING; then, once drained, RS AFTER / BARRIER and AG AFTER /
- * BARRIER. */
-static int rb_mesh_devwait(rb_ctx *x, void *rbuf, double lb0)
-{
-    ftar_comm *c = x->c;
-    const int L = x->steps, p = x->adjsize, v = x->vrank;
-    fdev_seg segs[FDEV_MAX_SEGS];
-    ftar_launched(c, FTAR_PH_LOOP, 0);
-    for (int s = 1; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_DURING);
-    for (int s = L - 1; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_BEFORE);
-    /* the call's token: the agree sequence number, uniform over the members and only growing */
-    const uint64_t token = c->job.seq;
-#ifdef FTAR_TEST_HOOKS
-    /* TEST-ONLY: this rank's flag published late (its peers' waits time out) */
-    if (getenv("FTAR_PEER_WAIT_DELAY_US")) {
-        ftar_drain(c); /* the tree done first: the delay is in the host, not on the device */
-        usleep((useconds_t)atoll(getenv("FTAR_PEER_WAIT_DELAY_US")));
-    }
-#endif
-    void *pf[FDEV_MAX_PEERS];
-    int np = 0;
-    for (int j = 1; j < p; j++) pf[np++] = ftar_flag(c, c->order[rb_real(x, v ^ j)]);
-    for (int i = 0; i < c->size; i++) /* FTAR_TRACE: each flag line is its owner's */
-        fdev_trace_region(c->dev, ftar_flag(c, c->order[i]), sizeof(c->job.shm->pwflag[0]), c->order[i], "PF");
-    if (fdev_peer_wait(c->dev, ftar_flag(c, c->wrank), pf, np, token, ftar_watch_peers, c)) {
-        fprintf(stderr, "ftar: rank %d: peer wait failed: %s\n", c->wrank, fdev_last_error());
-        ftar_ctrl_abort(&c->job, FTAR_ERR_DEVICE);
-    }
-    int ns = rb_mesh_ag_segs(x, rbuf, segs);
-    ftar_run(c, x->dtype, x->op, segs, ns, FDEV_TAG_STEP);
-    ftar_launched(c, FTAR_PH_AG, L - 1);
-    for (int s = L - 2; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_DURING);
-    ftar_drain_watch(c);
-    const int ran = fdev_peer_wait_verdict(c->dev);
-    if (!ran) c->stats.peer_wait_skips++;
-    ftar_exchange_done(c);
-    c->stats.step0_link_bytes += ftar_link_bytes(c) - lb0;
-    c->stats.steps += 2 * L;
-    c->stats.mesh_steps += 2;
-    c->stats.peer_waits++;
-    for (int s = 0; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_AFTER);
-    for (int s = 0; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_BARRIER);
-    for (int s = L - 1; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_AFTER);
-    for (int s = L - 1; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_BARRIER);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BEFORE);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_DURING);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_AFTER);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BARRIER);
-    /* the reduce-scatter's and the allgather's agree and the ERRORS_ARE_FATAL barrier: one
-     * round, which also carries every rank's verdict */
-    c->pubval = ran ? 0 : 1;
-    uint64_t newf = ftar_step_sync(c, 1);
-    c->pubval = 0;
-    if (newf) rb_handler_ag(x, newf, 0); /* no idle rank: aborts */
-    int any_skipped = 0;
-    for (int i = 0; i < c->size; i++) any_skipped |= ftar_peer_pub(c, c->order[i]) != 0;
-    if (any_skipped) {
-        if (!ran) {
-            ftar_run(c, x->dtype, x->op, segs, ns, FDEV_TAG_STEP);
-            ftar_drain(c);
-        }
-        newf = ftar_step_sync(c, 1);
-        if (newf) rb_handler_ag(x, newf, 0);
-    }
-    ftar_stats_end(c);
-    return FTAR_SUCCESS;
-}
-
-static int rb_mesh(rb_ctx *x, const void *sbuf, void *rbuf)
-{
-    ftar_comm *c = x->c;
-    const int L = x->steps, p = x->adjsize, v = x->vrank;
-    void *W = c->ws[WS_W];
-    int64_t own0 = x->rindex[L - 1], own_n = x->rcount[L - 1];
-    fdev_seg segs[FDEV_MAX_SEGS];
-    int ns = 0;
-
-    uint64_t newf;
-    if (x->push) {
-        rb_mesh_push_rs(x, sbuf, rbuf);
-        if (x->push == 2) return rb_mesh_push_finish(x, rbuf);
-        goto allgather;
-    }
-    /* reduce-scatter: T(v, L) over this rank's final block */
-    for (int s = 0; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_BEFORE);
-    ftar_enter(c);
-    const void *src[FDEV_MAX_TREE];
-    unsigned remote = 0;
-    for (int j = 0; j < p; j++) {
-        int u = v ^ j;
-        /* a peer's input: its sbuf in place, or its staged IN */
-        src[j] = j == 0 ? at(x, (void *)sbuf, own0) : at(x, ftar_buf(c, c->order[rb_real(x, u)], WS_IN), own0);
-        if (j) remote |= 1u << j;
-    }
-    double lb0 = ftar_link_bytes(c);
-    ftar_note_launch(c, src[1], (size_t)own_n * x->es);
-    /* the block goes to W, where the peers' allgather pulls it, and in the same pass to its
-     * place in rbuf (a second destination of the tree: one more local store of S/p), so the
-     * allgather only pulls the peers' blocks -- no local copy of this rank's own block, S/p
-     * fewer HBM reads per call (in place, rbuf's block is sbuf's, read by this lane only) */
-    void *own_out = at(x, rbuf, own0);
-    /* only where rbuf is co-aligned with W (a 16-byte vector body needs every operand at the
-     * same offset mod 16; otherwise the tree would fall back to scalar accesses): else the
-     * allgather copies the block out of W as before */
-    x->own_in_rbuf = x->io_safe && (((uintptr_t)own_out ^ (uintptr_t)at(x, W, own0)) & 15) == 0;
-    if (fdev_tree_out(c->dev, x->dtype, x->op, src, p, remote, at(x, W, own0), &own_out, x->own_in_rbuf, 0,
-                      (size_t)own_n, FDEV_TAG_STEP0)) {
-        fprintf(stderr, "ftar: rank %d: launch failed: %s\n", c->wrank, fdev_last_error());
-        ftar_ctrl_abort(&c->job, FTAR_ERR_DEVICE);
-    }
-    if (x->devwait) return rb_mesh_devwait(x, rbuf, lb0);
-    /* FTAR_OPT_MESH_WAIT=0: the allgather launched after the reduce-scatter's agree round.
-     * (Round 4's form with the allgather queued behind the tree behind a host-opened gate,
-     * FTAR_GATE_MAX >= S, was slower in every rehearsal and is superseded by the device wait:
-     * removed in round 6.) */
-    ftar_launched(c, FTAR_PH_LOOP, 0); /* every step's DURING point: the one launch is in flight */
-    for (int s = 1; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_DURING);
-    ftar_drain(c);
-    ftar_exchange_done(c);
-    c->stats.step0_link_bytes += ftar_link_bytes(c) - lb0;
-    c->stats.steps += L;
-    c->stats.mesh_steps++;
-    for (int s = 0; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_AFTER);
-    for (int s = 0; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_BARRIER);
-    newf = ftar_step_sync(c, 2); /* agree + barrier (:258-265) */
-    if (newf) rb_handler_rs(x, newf, L - 1); /* no idle rank: aborts */
-
-allgather:
-    /* allgather: every peer's final block into rbuf, this rank's own out of W */
-    for (int s = L - 1; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_BEFORE);
-    ftar_enter(c);
-    ns = rb_mesh_ag_segs(x, rbuf, segs);
-    ftar_run(c, x->dtype, x->op, segs, ns, FDEV_TAG_STEP);
-    ftar_launched(c, FTAR_PH_AG, L - 1);
-    for (int s = L - 2; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_DURING);
-    ftar_drain(c);
-    ftar_exchange_done(c);
-    c->stats.steps += L;
-    c->stats.mesh_steps++;
-    for (int s = L - 1; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_AFTER);
-    for (int s = L - 1; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_BARRIER);
-    /* The allgather's agree (:330-335) and the ERRORS_ARE_FATAL barrier (:357-360; no
-     * post-step at rem = 0) are one round: a failure seen at either ends the job the same
-     * way (no idle rank: errhandler_allgather aborts, new_entry = -1, :377-378), so the
-     * outcome of every kill point is unchanged. */
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BEFORE);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_DURING);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_AFTER);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BARRIER);
-    newf = ftar_step_sync(c, 2);
-    if (newf) rb_handler_ag(x, newf, 0); /* no idle rank: aborts */
-    ftar_stats_end(c);
-    return FTAR_SUCCESS;
-}
-
-/* One-shot mesh for small vectors: the allgather's data movement folded into the
- * reduce-scatter launch.  Each rank evaluates EVERY block in its owner's tree,
- * T(u, L) = tree over x_(u^j) (the same operands and order as rb_mesh's reduce-scatter,
- * so the same bits), straight into rbuf: one launch instead of two, (p-1) S link bytes
- * per rank instead of 2 (p-1) S / p -- cheaper below the size where a launch + drain
- * (~11 us) outweighs the extra link time.  Kill points and the two agree rounds are
- * rb_mesh's; with no idle rank a failure anywhere aborts. */
-/* The one-shot launch's operands as the peers' inputs stand now (ftar_buf: a peer's
- * exported sbuf once ftar_resolve_inputs mapped it, else its staged IN). */
-static void rb_oneshot_plan(rb_ctx *x, const void *sbuf, void *rbuf, struct rb_batch *B)
-{
-    ftar_comm *c = x->c;
-    const int L = x->steps, p = x->adjsize, v = x->vrank;
-    memset(B, 0, sizeof(*B));
-    for (int u = 0; u < p; u++) { /* block owned by vrank u */
-        int64_t ri[MAXSTEPS], si[MAXSTEPS], rc[MAXSTEPS], sc[MAXSTEPS];
-        rb_windows(u, x->count, L, ri, si, rc, sc);
-        const int64_t off = ri[L - 1];
-        B->out[u] = at(x, rbuf, off);
-        B->n[u] = (size_t)rc[L - 1];
-        for (int j = 0; j < p; j++) {
-            const int w = u ^ j;
-            if (w == v) {
-                B->src[u * p + j] = at(x, (void *)sbuf, off);
-            } else {
-                B->src[u * p + j] = at(x, ftar_buf(c, c->order[rb_real(x, w)], WS_IN), off);
-                B->remote[u] |= 1u << j;
-            }
-        }
-    }
-}
-
-/* Queue the one-shot launch right behind this rank's staging copy, before the barrier
- * after which the peers' staged inputs may be read: its workgroups wait on a gate that
- * rb_oneshot opens at the point where it would otherwise launch, so the launch latency
- * overlaps the staging drain and the barrier.  The plan assumes every peer stages its
- * input (this rank did, so the size is the same everywhere); rb_oneshot re-plans after
- * the inputs are resolved and skips the gated launch if anything differs. */
-static void rb_oneshot_prelaunch(rb_ctx *x, const void *sbuf, void *rbuf, void *stage_dst)
-{
-    ftar_comm *c = x->c;
-    x->gated = 0;
-    if (!c->gate) return;
-    rb_oneshot_plan(x, sbuf, rbuf, &x->gplan);
-    /* stage_dst: this rank's staging copy (sbuf -> IN) rides in the same launch, ahead of
-     * the gate -- one launch per call instead of two */
-    if (fdev_tree_batch_staged_gated(c->dev, x->dtype, x->op, x->gplan.src, x->adjsize, x->gplan.remote,
-                                     x->gplan.out, x->gplan.n, x->adjsize, FDEV_TAG_STEP0, stage_dst, sbuf,
-                                     stage_dst ? x->count : 0, &x->gated)) {
-        fprintf(stderr, "ftar: rank %d: launch failed: %s\n", c->wrank, fdev_last_error());
-        ftar_ctrl_abort(&c->job, FTAR_ERR_DEVICE);
-    }
-    if (x->gated) c->stats.gated_launches++;
-}
-
-static int rb_oneshot(rb_ctx *x, const void *sbuf, void *rbuf)
-{
-    ftar_comm *c = x->c;
-    const int L = x->steps, p = x->adjsize;
-    for (int s = 0; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_BEFORE);
-    ftar_enter(c);
-    struct rb_batch B;
-    rb_oneshot_plan(x, sbuf, rbuf, &B);
-    const void *const *src = B.src;
-    double lb0 = ftar_link_bytes(c);
-    for (int k = 0; k < p * p; k++) /* the first peer operand: the padding's re-pull source */
-        if (B.remote[k / p] & (1u << (k % p))) {
-            ftar_note_launch(c, src[k], B.n[k / p] * x->es);
-            break;
-        }
-    /* the queued launch runs now, or returns untouched and is replaced (also when another
-     * launch has given it up meanwhile) */
-    int pending = x->gated && fdev_gate_pending(c->dev);
-    int go = pending && memcmp(&B, &x->gplan, sizeof(B)) == 0;
-    if (x->gated && !go) c->stats.gated_skips++;
-    if (pending) fdev_gate_open(c->dev, !go);
-    x->gated = 0;
-    if (!go && fdev_tree_batch(c->dev, x->dtype, x->op, src, p, B.remote, B.out, B.n, p, FDEV_TAG_STEP0)) {
-        fprintf(stderr, "ftar: rank %d: launch failed: %s\n", c->wrank, fdev_last_error());
-        ftar_ctrl_abort(&c->job, FTAR_ERR_DEVICE);
-    }
-    ftar_launched(c, FTAR_PH_LOOP, 0);
-    for (int s = 1; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_DURING);
-    ftar_drain(c);
-    ftar_exchange_done(c);
-    c->stats.step0_link_bytes += ftar_link_bytes(c) - lb0;
-    c->stats.steps += 2 * L;
-    c->stats.mesh_steps++;
-    for (int s = 0; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_AFTER);
-    for (int s = 0; s < L; s++) ftar_maybe_die(c, FTAR_PH_LOOP, s, FTAR_PT_BARRIER);
-    /* The reduce-scatter's agree (:258-265), the allgather's (:330-335) and the
-     * ERRORS_ARE_FATAL barrier (:357-360) are one round here: the allgather's data moved in
-     * the same launch, and with no idle rank a failure seen at any of them ends the job the
-     * same way (both handlers abort, new_entry = -1, errhandler.c:207-211, 377-378) -- the
-     * kill points of every phase are passed before it, so each one's outcome is unchanged. */
-    for (int s = L - 1; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_BEFORE);
-    ftar_enter(c); /* the allgather's data already moved in the one launch */
-    ftar_launched(c, FTAR_PH_AG, L - 1);
-    for (int s = L - 2; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_DURING);
-    ftar_exchange_done(c);
-    for (int s = L - 1; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_AFTER);
-    for (int s = L - 1; s >= 0; s--) ftar_maybe_die(c, FTAR_PH_AG, s, FTAR_PT_BARRIER);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BEFORE);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_DURING);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_AFTER);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BARRIER);
-    uint64_t newf = ftar_step_sync(c, 1);
-    if (newf) rb_handler_rs(x, newf, L - 1); /* no idle rank: aborts */
-    ftar_stats_end(c);
-    return FTAR_SUCCESS;
-}
-
-int ftar_allreduce_rabenseifner(const void *sbuf, void *rbuf, size_t count, ftar_dtype dtype, ftar_op op,
-                                ftar_comm *c)
-{
-    if (!c) return FTAR_ERR_ARG;
-    rb_ctx X;
-    memset(&X, 0, sizeof(X));
-    rb_ctx *x = &X;
+    memset(x, 0, sizeof(*x));
     x->c = c;
     x->dtype = (int)dtype;
     x->op = (int)op;
@@ -842,21 +328,16 @@ int ftar_allreduce_rabenseifner(const void *sbuf, void *rbuf, size_t count, ftar
      * pinned flag words the wait also uses) */
     x->devwait = x->mesh && !x->oneshot && !x->push && c->mesh_wait && count >= (size_t)c->size &&
                  c->size - 1 <= FDEV_MAX_PEERS && fdev_get_knob(c->dev, FDEV_KNOB_FLAG_SYNC) == 1 && ftar_flag(c, c->wrank);
-    c->uin = sbuf;
-    c->uout = rbuf;
-    ftar_stats_begin(c);
-    c->stats.step0_copy = x->keep_recov && c->size > 1;
-    if (c->size == 1) return ftar_single_rank(c, sbuf, rbuf, count * x->es);
+    return FTAR_SUCCESS;
+}
 
-    size_t bytes = count * x->es;
-    ftar_ensure_workspace(c, bytes);
-    if (x->push) { /* uniform: the same geometry on every rank */
-        x->slot = rb_push_slot(x);
-        x->push = x->slot > 0;
-    }
-    void *IN = c->ws[WS_IN], *W = c->ws[WS_W], *T = c->ws[WS_T];
-    fdev_order_after(c->dev, c->user_stream); /* sbuf may still be in flight on the caller's stream */
-    rb_vrank(x);
+/* Input staging, up to the drain before the call's first barrier: what the peers read of this
+ * rank's input is its sbuf in place or a copy in IN.  Returns this rank's IN. */
+static void *rb_stage(rb_ctx *x, const void *sbuf, void *rbuf)
+{
+    ftar_comm *c = x->c;
+    const size_t count = x->count, bytes = count * x->es;
+    void *IN = c->ws[WS_IN];
     /* Where nothing writes this rank's IN -- every rank but the pre-step pairs; the
      * handlers only read it -- the peers read sbuf in place; otherwise, or when its
      * memory cannot be shared, it is staged in IN.  With a spare, the partner's step-0
@@ -875,12 +356,9 @@ int ftar_allreduce_rabenseifner(const void *sbuf, void *rbuf, size_t count, ftar
                                    x->oneshot ? disjoint : (x->fast_io || (x->rank >= 2 * x->rem && disjoint)));
     if (x->push) {
         ftar_inputs_done(c);
-        rb_windows(x->vrank, count, x->steps, x->rindex, x->sindex, x->rcount, x->scount);
     } else if (aliased) {
         IN = (void *)sbuf;
-        rb_windows(x->vrank, count, x->steps, x->rindex, x->sindex, x->rcount, x->scount);
     } else if (x->oneshot) {
-        rb_windows(x->vrank, count, x->steps, x->rindex, x->sindex, x->rcount, x->scount);
         /* small inputs are staged by every rank (ftar_stage_input): the launch's operands
          * are known before the barrier, and the staging copy can ride in it */
         if (bytes <= c->stage_max) {
@@ -892,21 +370,25 @@ int ftar_allreduce_rabenseifner(const void *sbuf, void *rbuf, size_t count, ftar
             if (bytes <= c->stage_max) rb_oneshot_prelaunch(x, sbuf, rbuf, NULL);
         }
     } else if (x->mesh) { /* peers pull every block of sbuf but this rank's own final one */
-        rb_windows(x->vrank, count, x->steps, x->rindex, x->sindex, x->rcount, x->scount);
         int64_t b0 = x->rindex[x->steps - 1], b1 = b0 + x->rcount[x->steps - 1];
         fdev_seg cp[2] = {{FDEV_COPY, 0, IN, sbuf, NULL, (size_t)b0, NULL},
                           {FDEV_COPY, 0, at(x, IN, b1), at(x, (void *)sbuf, b1), NULL, (size_t)((int64_t)count - b1),
                            NULL}};
         ftar_run(c, x->dtype, x->op, cp, 2, FDEV_TAG_LOCAL);
     } else if (x->fast_io) { /* the half of sbuf peers pull at step 0 */
-        rb_windows(x->vrank, count, x->steps, x->rindex, x->sindex, x->rcount, x->scount);
         run_copy(x, at(x, IN, x->sindex[0]), at(x, (void *)sbuf, x->sindex[0]), x->scount[0], 0, FDEV_TAG_LOCAL);
     } else {
         run_copy(x, IN, sbuf, (int64_t)count, 0, FDEV_TAG_LOCAL); /* rbuf = sbuf, :35-42 */
     }
     ftar_drain(c);
+    return IN;
+}
 
-    /* ---- pre-step (:61-139): failures are fatal here ---- */
+/* ---- pre-step (:61-139): failures are fatal here ---- */
+static void rb_pre_step(rb_ctx *x, void *IN)
+{
+    ftar_comm *c = x->c;
+    const size_t count = x->count;
     ftar_maybe_die(c, FTAR_PH_PRE, 0, FTAR_PT_BEFORE);
     if (x->fast_io) {
         ftar_enter(c);
@@ -945,15 +427,15 @@ int ftar_allreduce_rabenseifner(const void *sbuf, void *rbuf, size_t count, ftar
             run_copy(x, at(x, IN, lh), at(x, P, lh), rh, FDEV_REMOTE_X, FDEV_TAG_STEP);
             ftar_drain(c);
         }
-        if (x->vrank != -1)
-            rb_windows(x->vrank, count, x->steps, x->rindex, x->sindex, x->rcount, x->scount);
         ftar_sync_fatal(c); /* MPI_Barrier before the tolerant region (:166) */
     }
+}
 
-    if (x->oneshot) return rb_oneshot(x, sbuf, rbuf);
-    if (x->mesh) return rb_mesh(x, sbuf, rbuf);
-
-    /* ---- reduce-scatter (:170-284) ---- */
+/* ---- reduce-scatter (:170-284) ---- */
+static void rb_reduce_scatter(rb_ctx *x)
+{
+    ftar_comm *c = x->c;
+    void *T = c->ws[WS_T];
     for (int v = 0; v < x->adjsize; v++) x->in0_w[v] = c->order[rb_real(x, v)];
     int step = 0;
     for (int mask = 1; mask < x->adjsize; mask <<= 1, step++) {
@@ -1022,9 +504,14 @@ int ftar_allreduce_rabenseifner(const void *sbuf, void *rbuf, size_t count, ftar
             rb_handler_rs(x, newf, step);
         }
     }
+}
 
-    /* ---- allgather (:299-355) ---- */
-    step = x->steps - 1;
+/* ---- allgather (:299-355) ---- */
+static void rb_allgather(rb_ctx *x, void *rbuf)
+{
+    ftar_comm *c = x->c;
+    void *W = c->ws[WS_W];
+    int step = x->steps - 1;
     for (int mask = x->adjsize >> 1; mask > 0; mask >>= 1, step--) {
         ftar_plan P;
         ftar_xstate xs;
@@ -1054,17 +541,19 @@ int ftar_allreduce_rabenseifner(const void *sbuf, void *rbuf, size_t count, ftar
             rb_handler_ag(x, newf, step);
         }
     }
+}
 
+/* ---- ERRORS_ARE_FATAL barrier + post-step (:357-381) ---- */
+static int rb_epilogue(rb_ctx *x, void *IN, void *rbuf)
+{
+    ftar_comm *c = x->c;
+    const size_t count = x->count;
+    void *W = c->ws[WS_W];
     if (x->bg_pending) { /* peers read our IN until their copies are done: join before the barrier */
         ftar_drain_bg(c);
         x->bg_pending = 0;
     }
-
-    /* ---- ERRORS_ARE_FATAL barrier + post-step (:357-381) ---- */
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BEFORE);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_DURING);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_AFTER);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BARRIER);
+    ftar_pass_post(c);
     ftar_sync_fatal(c);
     if (x->fast_io) { /* rbuf is complete; no idle rank reads W, every peer is done with it */
         ftar_stats_end(c);
@@ -1081,6 +570,39 @@ int ftar_allreduce_rabenseifner(const void *sbuf, void *rbuf, size_t count, ftar
     ftar_sync_fatal(c); /* peers are done reading our W before it is reused */
     ftar_stats_end(c);
     return FTAR_SUCCESS;
+}
+
+int ftar_allreduce_rabenseifner(const void *sbuf, void *rbuf, size_t count, ftar_dtype dtype, ftar_op op,
+                                ftar_comm *c)
+{
+    if (!c) return FTAR_ERR_ARG;
+    rb_ctx X;
+    rb_ctx *x = &X;
+    int rc = rb_select_form(x, sbuf, rbuf, count, dtype, op, c);
+    if (rc) return rc;
+    c->uin = sbuf;
+    c->uout = rbuf;
+    ftar_stats_begin(c);
+    c->stats.step0_copy = x->keep_recov && c->size > 1;
+    if (c->size == 1) return ftar_single_rank(c, sbuf, rbuf, count * x->es);
+
+    ftar_ensure_workspace(c, count * x->es);
+    if (x->push) { /* uniform: the same geometry on every rank */
+        x->slot = rb_push_slot(x);
+        x->push = x->slot > 0;
+    }
+    fdev_order_after(c->dev, c->user_stream); /* sbuf may still be in flight on the caller's stream */
+    rb_vrank(x);
+    /* this rank's windows of every step: a function of vrank, count and steps alone (an idle
+     * odd rank of a pre-step pair, vrank -1, has none until a handler gives it a role) */
+    if (x->vrank != -1) rb_windows(x->vrank, count, x->steps, x->rindex, x->sindex, x->rcount, x->scount);
+    void *IN = rb_stage(x, sbuf, rbuf);
+    rb_pre_step(x, IN);
+    if (x->oneshot) return rb_oneshot(x, sbuf, rbuf);
+    if (x->mesh) return rb_mesh(x, sbuf, rbuf);
+    rb_reduce_scatter(x);
+    rb_allgather(x, rbuf);
+    return rb_epilogue(x, IN, rbuf);
 }
 
 int ftar_allreduce_rabenseifner_host(const void *sbuf, void *rbuf, size_t count, ftar_dtype dtype, ftar_op op,

@@ -343,10 +343,7 @@ int ftar_recursive_doubling(const void *src, void *dst, size_t count, ftar_dtype
     }
 
     /* ERRORS_ARE_FATAL barrier (:73-75), then the fan-out to inactive ranks (:78-89) */
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BEFORE);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_DURING);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_AFTER);
-    ftar_maybe_die(c, FTAR_PH_POST, 0, FTAR_PT_BARRIER);
+    ftar_pass_post(c);
     ftar_sync_fatal(c);
     if (x->ninactive > x->nactive) ftar_abort(c, 1); /* reference: inactive ranks wait forever */
     int ii = index_of(x->inactive, x->ninactive, me);

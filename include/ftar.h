@@ -186,7 +186,12 @@ int ftar_set_reduce_variant(int variant);
 /* Stream the comm orders its work after (hipStream_t, NULL = null stream). */
 int ftar_comm_set_stream(ftar_comm *comm, void *stream);
 
-/* Transport options (defaults come from the FTAR_* environment at init).  Collective:
+/* Transport options.  Defaults come from the FTAR_* environment at init, where each variable
+ * must be a number inside its own range (a whole number unless a time): anything else makes
+ * ftar_init_rank return FTAR_ERR_ARG.  ftar_comm_set_option is laxer: it refuses an unknown
+ * id and a negative, NaN or infinite value, reads any non-zero value of a 0/1 option as 1 and
+ * FTAR_OPT_PUSH >= 2 as 2, stores sizes and times as given, and keeps to the environment's
+ * range only for FTAR_OPT_REDUNDANCY (0, 1, 2) and FTAR_OPT_TREE_UNROLL (1, 2, 4).  Collective:
  * every live rank of the comm must set the same value before its next call. */
 typedef enum {
     FTAR_OPT_OVERLAP = 0,      /* Raben step-0 redundancy copy on a background stream (0/1) */
@@ -228,9 +233,10 @@ typedef enum {
                                   the launch waits on up to half the CUs -- slower on a GPU shared by
                                   several ranks, so bench.py times it on the node */
     FTAR_OPT_MESH_WAIT = 13    /* the mesh's allgather queued right behind its reduce-scatter, ordered on
-                                  the device: each rank publishes a flag in its HBM once its tree is
-                                  released, and the allgather waits for the peers' flags instead of a
-                                  host agree round and a drain (0/1, default 1) */
+                                  the device: each rank publishes a flag in its line of the control block's
+                                  flag page (host memory every GPU maps) once its tree is released, and
+                                  the allgather waits for the peers' flags instead of a host agree round
+                                  and a drain (0/1, default 1) */
 } ftar_option;
 
 int ftar_comm_set_option(ftar_comm *comm, ftar_option opt, double value);

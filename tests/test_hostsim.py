@@ -32,7 +32,7 @@ def _cmp(oracle_fn, algo, inputs, kills=(), op=0, env=None):
         assert r.aborted and not r.outputs, (kills, r.stderr[-1000:])
         # the same abort: the handlers' MPI_Abort codes (1 Raben, 16 RD check_abort), 75 where a
         # region under ERRORS_ARE_FATAL sees the failure.  Raben at rem = 0 holds the allgather's
-        # last agree and the fatal barrier as one round (ftar_raben.c rb_mesh): a death between
+        # last agree and the fatal barrier as one round (ftar_raben_mesh.c rb_mesh): a death between
         # them (POST) is seen by the allgather's handler there, which aborts with its own code
         codes = {o.abort_code}
         if algo == "raben" and o.abort_code == 75 and any(k[1] == 3 for k in kills):
@@ -463,6 +463,43 @@ def test_mesh_parity(hostsim, oracle, p, dtype, op, form):
         assert all(r.status[w][0][7] == rh.status[w][0][7] - 1 for w in r.status), (r.status, rh.status)
         assert all(st[0][15] == 1 and st[0][16] == 0 for st in r.status.values()), r.status  # peer_waits, skips
         assert all(st[0][15] == 0 for st in rh.status.values()), rh.status
+
+
+# Every rank's integer ftar_stats of one call, as literals (the tests above only compare forms
+# with each other).  Recorded with this probe at commit 4657721, identical in three consecutive
+# runs there; no integer field the probe reports per call had to be left out.
+#   form: (p, env, {world rank: (steps, mesh_steps, syncs, kernels, peer_waits, peer_wait_skips,
+#                                gated_launches, gated_skips, recoveries)})
+_PIN = {"FTAR_MESH": "1", "FTAR_TREE_UNROLL": "1", "FTAR_GATE": "0"}
+FORM_STATS = {
+    "mesh_wait1": (4, dict(_PIN, FTAR_ONESHOT_MAX="0", FTAR_PUSH="0", FTAR_MESH_WAIT="1"),
+                   {w: (4, 2, 5, 3, 1, 0, 0, 0, 0) for w in range(4)}),
+    "mesh_wait0": (4, dict(_PIN, FTAR_ONESHOT_MAX="0", FTAR_PUSH="0", FTAR_MESH_WAIT="0"),
+                   {w: (4, 2, 6, 3, 0, 0, 0, 0, 0) for w in range(4)}),
+    "oneshot": (4, dict(_PIN, FTAR_ONESHOT_MAX=str(1 << 20), FTAR_PUSH="0", FTAR_MESH_WAIT="1"),
+                {w: (4, 1, 5, 2, 0, 0, 0, 0, 0) for w in range(4)}),
+    "push": (4, dict(_PIN, FTAR_ONESHOT_MAX="0", FTAR_PUSH="1", FTAR_MESH_WAIT="1"),
+             {w: (4, 2, 7, 3, 0, 0, 0, 0, 0) for w in range(4)}),
+    # FTAR_PUSH=2 as it runs today, which is push 1: `x->push = x->slot > 0` (ftar_raben.c) turns
+    # the 2 into 1, so this row -- like every push2 case of this file -- does NOT cover the
+    # push-2 branches of rb_mesh_push_rs / rb_mesh_push_finish
+    "push2": (4, dict(_PIN, FTAR_ONESHOT_MAX="0", FTAR_PUSH="2", FTAR_MESH_WAIT="1"),
+              {w: (4, 2, 7, 3, 0, 0, 0, 0, 0) for w in range(4)}),
+    # the step-by-step schedule, one spare: rank 1 idles through the loops
+    "steps_p5": (5, dict(_PIN, FTAR_ONESHOT_MAX="0", FTAR_PUSH="0", FTAR_MESH_WAIT="1"),
+                 {0: (5, 0, 12, 8, 0, 0, 0, 0, 0), 1: (2, 0, 12, 3, 0, 0, 0, 0, 0), 2: (4, 0, 12, 6, 0, 0, 0, 0, 0),
+                  3: (4, 0, 12, 6, 0, 0, 0, 0, 0), 4: (4, 0, 12, 6, 0, 0, 0, 0, 0)}),
+}
+
+
+@pytest.mark.parametrize("form", sorted(FORM_STATS))
+def test_form_stats_pinned(hostsim, oracle, form):
+    """Steps, mesh exchanges, agree rounds, launches, peer waits, gated launches (FTAR_GATE=0)
+    and recoveries of every form at count 4099: the literal values, on every rank."""
+    p, env, want = FORM_STATS[form]
+    o, r = _cmp(oracle.rabenseifner, "raben", oracle.random_inputs(p, 4099, seed=p), env=env)
+    got = {w: tuple(st[0][i] for i in (17, 9, 7, 18, 15, 16, 10, 11, 3)) for w, st in r.status.items()}
+    assert got == want
 
 
 @pytest.mark.parametrize("p,late", [(4, 3), (8, 0), (2, 1)])

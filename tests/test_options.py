@@ -8,7 +8,9 @@ import pytest
 
 @pytest.fixture
 def solo(hostsim, monkeypatch):
-    for k in ("FTAR_RELAY", "FTAR_RELAY_MIN", "FTAR_OVERLAP", "FTAR_COPY_ENGINE", "FTAR_REDUNDANCY"):
+    for k in ("FTAR_RELAY", "FTAR_RELAY_MIN", "FTAR_OVERLAP", "FTAR_COPY_ENGINE", "FTAR_REDUNDANCY", "FTAR_LOOP_SECONDS",
+              "FTAR_MESH", "FTAR_ONESHOT_MAX", "FTAR_PUSH", "FTAR_GATE", "FTAR_FLAG_SYNC", "FTAR_TREE_UNROLL",
+              "FTAR_GATE_MAX", "FTAR_MESH_WAIT"):
         monkeypatch.delenv(k, raising=False)
     monkeypatch.setenv("FTAR_HOSTSIM_TAG", f"opt{os.getpid()}")
     L = ctypes.CDLL(os.path.join(hostsim, "libftar_hostsim.so"))
@@ -41,6 +43,35 @@ def test_option_defaults_and_roundtrip(solo):
                      (11, 2), (11, 4), (11, 1), (12, 16 << 20), (12, 0)):
         assert L.ftar_comm_set_option(h, opt, val) == 0
         assert _get(L, h, opt) == val
+
+
+def test_option_roundtrip_every_id(solo):
+    """Every ftar_option id: its default, a set, the value read back, and the default again."""
+    L, h = solo
+    MiB = 1 << 20
+    dflt = {0: 1, 1: 1, 2: 4 * MiB, 3: 0, 4: 0, 5: 2, 6: 1, 7: MiB, 8: 0, 9: 1, 10: 1, 11: 1, 12: MiB, 13: 1}
+    new = {0: 0, 1: 0, 2: MiB, 3: 0.5, 4: 1, 5: 1, 6: 0, 7: 4096, 8: 2, 9: 0, 10: 0, 11: 2, 12: 16 * MiB, 13: 0}
+    assert sorted(dflt) == sorted(new) == list(range(14))
+    assert L.ftar_comm_set_option(h, 14, 1) == 13  # one past the last id
+    for opt in range(14):
+        assert _get(L, h, opt) == dflt[opt], opt
+        for val in (new[opt], dflt[opt]):
+            assert L.ftar_comm_set_option(h, opt, val) == 0, (opt, val)
+            assert _get(L, h, opt) == val, (opt, val)
+    # what a set normalises: a switch to v != 0, the push level saturating at 2
+    for opt, val, want in ((6, 7, 1), (9, 0.5, 1), (13, 3, 1), (8, 1, 1), (8, 0.5, 1), (8, 5, 2), (7, 4096.75, 4096)):
+        assert L.ftar_comm_set_option(h, opt, val) == 0, (opt, val)
+        assert _get(L, h, opt) == want, (opt, val)
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")])
+@pytest.mark.parametrize("opt", [6, 7, 3])  # a boolean, a size, the decimal option
+def test_option_nan_inf_refused(solo, opt, bad):
+    """A NaN or infinite value is FTAR_ERR_ARG and leaves the stored value as it was."""
+    L, h = solo
+    before = _get(L, h, opt)
+    assert L.ftar_comm_set_option(h, opt, bad) == 13
+    assert _get(L, h, opt) == before
 
 
 def test_option_errors(solo):

@@ -49,6 +49,15 @@ def _run(oracle, algo, ins, kills=(), env=None, iters=1):
                 assert np.array_equal(r.outputs[w][it].view(np.uint32), o.outputs[w].view(np.uint32)), (w, it)
 
 
+def test_rb_block_matches_rb_windows(asan_build):
+    """rb_block (a vrank's final block by the halving rule, what the mesh forms plan with)
+    equals rb_windows' last-step rindex / rcount: every vrank of p = 2, 4, 8, 16, 32, counts
+    1, 3, 17 (empty blocks), 1031, 4099 and 2^31 + 5; a stand-alone program under the sanitizers
+    (tests/hostsim/rb_block_check.c)."""
+    cp = subprocess.run([os.path.join(asan_build, "bin", "rb_block_check")], capture_output=True, text=True, timeout=60)
+    assert cp.returncode == 0 and "372 blocks checked, 0 differ" in cp.stdout, (cp.stdout, cp.stderr)
+
+
 @pytest.mark.parametrize("algo", ["raben", "rd"])
 @pytest.mark.parametrize("p", [1, 2, 3, 5, 8, 9])
 def test_asan_nofault(asan_build, oracle, algo, p):
