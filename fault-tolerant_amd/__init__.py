@@ -21,6 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libftar.so")
 
 INT32, FLOAT32, INT64, FLOAT64 = 0, 1, 2, 3
+FLOAT16, BFLOAT16 = 16, 17  # 2-byte floats: SUM / PROD / MAX / MIN, rounded in their own format at every combination
 SUM, PROD, MAX, MIN = 0, 1, 2, 3
 LAND, BAND, LOR, BOR, LXOR, BXOR = 4, 5, 6, 7, 8, 9  # MPI logical / bitwise ops (integer types)
 PH_PRE, PH_LOOP, PH_AG, PH_POST = 0, 1, 2, 3
@@ -130,7 +131,8 @@ def lib():
 
 def _dtype_of(t) -> int:
     import torch
-    m = {torch.int32: INT32, torch.float32: FLOAT32, torch.int64: INT64, torch.float64: FLOAT64}
+    m = {torch.int32: INT32, torch.float32: FLOAT32, torch.int64: INT64, torch.float64: FLOAT64,
+         torch.float16: FLOAT16, torch.bfloat16: BFLOAT16}
     if t.dtype not in m:
         raise FtarError(f"unsupported dtype {t.dtype}")
     return m[t.dtype]

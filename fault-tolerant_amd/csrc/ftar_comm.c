@@ -35,8 +35,16 @@ size_t ftar_esize(int dtype)
     case FTAR_FLOAT32: return 4;
     case FTAR_INT64:
     case FTAR_FLOAT64: return 8;
+    case FTAR_FLOAT16:
+    case FTAR_BFLOAT16: /* only where the device layer has them (ftar_dev.h) */
+        return (fdev_has_dtype && fdev_has_dtype(dtype)) ? 2 : 0;
     default: return 0;
     }
+}
+
+static int is_float_type(int dtype)
+{
+    return dtype == FTAR_FLOAT32 || dtype == FTAR_FLOAT64 || dtype == FTAR_FLOAT16 || dtype == FTAR_BFLOAT16;
 }
 
 /* MPI_Reduce_local's type/op check: an unknown type or op is an argument error, a
@@ -44,7 +52,7 @@ size_t ftar_esize(int dtype)
 int ftar_check_op(int dtype, int op)
 {
     if (ftar_esize(dtype) == 0 || op < FTAR_SUM || op >= FTAR_NOPS) return FTAR_ERR_ARG;
-    if (op >= FTAR_LAND && (dtype == FTAR_FLOAT32 || dtype == FTAR_FLOAT64)) return FTAR_ERR_OP;
+    if (op >= FTAR_LAND && is_float_type(dtype)) return FTAR_ERR_OP;
     return FTAR_SUCCESS;
 }
 

@@ -223,6 +223,11 @@ void fdev_trace_note(ftar_dev *d, const char *fmt, ...) __attribute__((format(pr
 int fdev_reduce_local(const void *in, void *inout, size_t n, int dtype, int op, void *stream);
 int fdev_set_reduce_variant(int v);
 
+/* 1 if the device layer has kernels for element type `dtype`.  Weak: a device layer that
+ * does not define it (the host-sim test layer) has the four original types only, and the
+ * shared host C then refuses the 2-byte float types at the boundary (ftar_esize). */
+int fdev_has_dtype(int dtype) __attribute__((weak));
+
 const char *fdev_last_error(void);
 
 #ifdef __cplusplus

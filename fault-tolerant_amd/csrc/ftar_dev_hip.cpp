@@ -68,6 +68,8 @@ int set_err(hipError_t e, const char *what)
 size_t esize_of(int dtype)
 {
     switch (dtype) {
+    case ftar::kFloat16:
+    case ftar::kBFloat16: return 2;
     case ftar::kInt32:
     case ftar::kFloat32: return 4;
     case ftar::kInt64:
@@ -506,6 +508,9 @@ int check_local_ptr(const void *ptr, size_t bytes, int dev)
 } // namespace fdevi
 
 extern "C" {
+
+// every element type the kernels are instantiated for (ftar_dev.h)
+int fdev_has_dtype(int dtype) { return esize_of(dtype) != 0; }
 
 int fdev_reduce_local(const void *in, void *inout, size_t n, int dtype, int op, void *stream)
 {

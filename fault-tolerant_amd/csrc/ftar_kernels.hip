@@ -39,6 +39,12 @@ template <typename T> struct Arith { using U = T; };
 template <> struct Arith<int32_t> { using U = uint32_t; };
 template <> struct Arith<int64_t> { using U = uint64_t; };
 
+// The 2-byte float types: plain bit containers (sizeof == 2 gives 8 elements per 16-byte
+// vector); the arithmetic is in the apply / apply16 overloads below.
+struct f16_t { uint16_t b; };
+struct bf16_t { uint16_t b; };
+static_assert(sizeof(f16_t) == 2 && sizeof(bf16_t) == 2, "2-byte elements");
+
 template <typename T, int OP>
 __device__ __forceinline__ T apply(T x, T y)
 {
@@ -55,6 +61,51 @@ __device__ __forceinline__ T apply(T x, T y)
     else if constexpr (OP == kLxor) return (T)((x != 0) != (y != 0));
     else return (T)(x ^ y);
 }
+
+// float16: the arithmetic is the hardware's own binary16 (v_add_f16 / v_mul_f16: one
+// correctly rounded IEEE operation, subnormals kept -- the f16 denormal mode is on).  MAX /
+// MIN are compare-and-select like every other type: the result is one of the two operands
+// bit for bit (v_max_f16 / v_min_f16 would return +0 or -0 by their own rule and quiet a NaN).
+template <int OP>
+__device__ __forceinline__ f16_t apply_f16(f16_t x, f16_t y)
+{
+    _Float16 a, b;
+    __builtin_memcpy(&a, &x, 2);
+    __builtin_memcpy(&b, &y, 2);
+    if constexpr (OP == kSum) a = a + b;
+    else if constexpr (OP == kProd) a = a * b;
+    else if constexpr (OP == kMax) return (a > b) ? x : y;
+    else return (a < b) ? x : y;
+    f16_t r;
+    __builtin_memcpy(&r, &a, 2);
+    return r;
+}
+template <> __device__ __forceinline__ f16_t apply<f16_t, kSum>(f16_t x, f16_t y) { return apply_f16<kSum>(x, y); }
+template <> __device__ __forceinline__ f16_t apply<f16_t, kProd>(f16_t x, f16_t y) { return apply_f16<kProd>(x, y); }
+template <> __device__ __forceinline__ f16_t apply<f16_t, kMax>(f16_t x, f16_t y) { return apply_f16<kMax>(x, y); }
+template <> __device__ __forceinline__ f16_t apply<f16_t, kMin>(f16_t x, f16_t y) { return apply_f16<kMin>(x, y); }
+
+// bfloat16: widened to float32 (exact: the 16 bits are the float's upper half), one float32
+// operation, rounded once to nearest even (v_cvt_pk_bf16_f32 on gfx950).  The float32 result
+// of a SUM or PROD of two bfloat16 values carries 24 >= 2 * 8 + 2 significand bits, so the
+// second rounding gives the correctly rounded bfloat16 result.  MAX / MIN compare the widened
+// values and return the chosen operand's own bits.
+__device__ __forceinline__ float bf16_widen(bf16_t v) { return __builtin_bit_cast(float, (uint32_t)v.b << 16); }
+template <int OP>
+__device__ __forceinline__ bf16_t apply_bf16(bf16_t x, bf16_t y)
+{
+    const float a = bf16_widen(x), b = bf16_widen(y);
+    if constexpr (OP == kMax) return (a > b) ? x : y;
+    else if constexpr (OP == kMin) return (a < b) ? x : y;
+    else {
+        const __bf16 r = (__bf16)(OP == kSum ? a + b : a * b);
+        return bf16_t{__builtin_bit_cast(uint16_t, r)};
+    }
+}
+template <> __device__ __forceinline__ bf16_t apply<bf16_t, kSum>(bf16_t x, bf16_t y) { return apply_bf16<kSum>(x, y); }
+template <> __device__ __forceinline__ bf16_t apply<bf16_t, kProd>(bf16_t x, bf16_t y) { return apply_bf16<kProd>(x, y); }
+template <> __device__ __forceinline__ bf16_t apply<bf16_t, kMax>(bf16_t x, bf16_t y) { return apply_bf16<kMax>(x, y); }
+template <> __device__ __forceinline__ bf16_t apply<bf16_t, kMin>(bf16_t x, bf16_t y) { return apply_bf16<kMin>(x, y); }
 
 // Runs fn(std::integral_constant<int, OP>) for the runtime op: one instantiation per op
 // the element type has (the logical / bitwise ops only for the integer types).
@@ -97,6 +148,59 @@ __device__ __forceinline__ uint4 apply16(uint4 a, uint4 b)
     __builtin_memcpy(&r, xa, 16);
     return r;
 }
+
+// The 16-bit types' vector path, two elements per 32-bit register.
+typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+typedef float f2_t __attribute__((ext_vector_type(2)));
+typedef __bf16 b2_t __attribute__((ext_vector_type(2)));
+
+// SUM / PROD of float16 pairs: packed binary16 math (v_pk_add_f16 / v_pk_mul_f16)
+template <int OP>
+__device__ __forceinline__ uint32_t pk_f16(uint32_t a, uint32_t b)
+{
+    const h2_t x = __builtin_bit_cast(h2_t, a), y = __builtin_bit_cast(h2_t, b);
+    return __builtin_bit_cast(uint32_t, OP == kSum ? x + y : x * y);
+}
+// SUM / PROD of bfloat16 pairs: the low element widened by a shift, the high one by a mask,
+// packed float32 math (v_pk_add_f32 / v_pk_mul_f32), one packed conversion back
+template <int OP>
+__device__ __forceinline__ uint32_t pk_bf16(uint32_t a, uint32_t b)
+{
+    const f2_t x = {__builtin_bit_cast(float, a << 16), __builtin_bit_cast(float, a & 0xffff0000u)};
+    const f2_t y = {__builtin_bit_cast(float, b << 16), __builtin_bit_cast(float, b & 0xffff0000u)};
+    const f2_t r = OP == kSum ? x + y : x * y;
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(r, b2_t));
+}
+// MAX / MIN of a pair: each half selected whole from a or b
+template <typename T, int OP>
+__device__ __forceinline__ uint32_t pk_sel(uint32_t a, uint32_t b)
+{
+    const T lo = apply<T, OP>(T{(uint16_t)a}, T{(uint16_t)b});
+    const T hi = apply<T, OP>(T{(uint16_t)(a >> 16)}, T{(uint16_t)(b >> 16)});
+    return (uint32_t)lo.b | ((uint32_t)hi.b << 16);
+}
+template <typename T, int OP>
+__device__ __forceinline__ uint32_t pk16(uint32_t a, uint32_t b)
+{
+    if constexpr (OP == kMax || OP == kMin) return pk_sel<T, OP>(a, b);
+    else if constexpr (std::is_same<T, f16_t>::value) return pk_f16<OP>(a, b);
+    else return pk_bf16<OP>(a, b);
+}
+#define FTAR_APPLY16_PK(T, OP)                                                                                 \
+    template <> __device__ __forceinline__ uint4 apply16<T, OP>(uint4 a, uint4 b)                              \
+    {                                                                                                          \
+        return make_uint4(pk16<T, OP>(a.x, b.x), pk16<T, OP>(a.y, b.y), pk16<T, OP>(a.z, b.z),                 \
+                          pk16<T, OP>(a.w, b.w));                                                              \
+    }
+FTAR_APPLY16_PK(f16_t, kSum)
+FTAR_APPLY16_PK(f16_t, kProd)
+FTAR_APPLY16_PK(f16_t, kMax)
+FTAR_APPLY16_PK(f16_t, kMin)
+FTAR_APPLY16_PK(bf16_t, kSum)
+FTAR_APPLY16_PK(bf16_t, kProd)
+FTAR_APPLY16_PK(bf16_t, kMax)
+FTAR_APPLY16_PK(bf16_t, kMin)
+#undef FTAR_APPLY16_PK
 
 // ---------------------------------------------------------------------------------
 // segment kernel
@@ -170,6 +274,7 @@ __device__ __forceinline__ bool stage_copy_vec(const KSignal &G)
     if (blockIdx.x == 0)
         for (size_t i = done + threadIdx.x; i < G.stage_n; i += blockDim.x) {
             if (G.stage_es == 8) ((unsigned long long *)G.stage_dst)[i] = ((const unsigned long long *)G.stage_src)[i];
+            else if (G.stage_es == 2) ((unsigned short *)G.stage_dst)[i] = ((const unsigned short *)G.stage_src)[i];
             else ((unsigned *)G.stage_dst)[i] = ((const unsigned *)G.stage_src)[i];
         }
     return true;
@@ -180,6 +285,7 @@ __device__ __forceinline__ void signal_stage(const KSignal &G)
     if (!G.stage_dst) return;
     if (stage_copy_vec(G)) {
     } else if (G.stage_es == 8) stage_copy<unsigned long long>(G);
+    else if (G.stage_es == 2) stage_copy<unsigned short>(G);
     else stage_copy<unsigned>(G);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -540,6 +646,8 @@ hipError_t launch_tree(int dtype, int op, int p, const TreeArgs &A, unsigned gri
     case kFloat32: return launch_tree_t<float>(op, p, A, grid, s);
     case kInt64: return launch_tree_t<int64_t>(op, p, A, grid, s);
     case kFloat64: return launch_tree_t<double>(op, p, A, grid, s);
+    case kFloat16: return launch_tree_t<f16_t>(op, p, A, grid, s);
+    case kBFloat16: return launch_tree_t<bf16_t>(op, p, A, grid, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -611,6 +719,8 @@ hipError_t launch_tree_batch(int dtype, int op, int p, const TreeBatch &B, unsig
     case kFloat32: return launch_batch_t<float>(op, p, B, grid, s);
     case kInt64: return launch_batch_t<int64_t>(op, p, B, grid, s);
     case kFloat64: return launch_batch_t<double>(op, p, B, grid, s);
+    case kFloat16: return launch_batch_t<f16_t>(op, p, B, grid, s);
+    case kBFloat16: return launch_batch_t<bf16_t>(op, p, B, grid, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -670,6 +780,8 @@ hipError_t launch_segments(int dtype, int op, const KSegList &L, unsigned grid, 
     case kFloat32: return launch_t<float>(op, L, grid, s);
     case kInt64: return launch_t<int64_t>(op, L, grid, s);
     case kFloat64: return launch_t<double>(op, L, grid, s);
+    case kFloat16: return launch_t<f16_t>(op, L, grid, s);
+    case kBFloat16: return launch_t<bf16_t>(op, L, grid, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -695,6 +807,8 @@ hipError_t launch_reduce_lds(int dtype, int op, void *inout, const void *in, siz
     case kFloat32: return launch_lds_t<float>(op, io, i, nvec, grid, s, nts);
     case kInt64: return launch_lds_t<int64_t>(op, io, i, nvec, grid, s, nts);
     case kFloat64: return launch_lds_t<double>(op, io, i, nvec, grid, s, nts);
+    case kFloat16: return launch_lds_t<f16_t>(op, io, i, nvec, grid, s, nts);
+    case kBFloat16: return launch_lds_t<bf16_t>(op, io, i, nvec, grid, s, nts);
     default: return hipErrorInvalidValue;
     }
 }

@@ -3,7 +3,13 @@
  * of bench.py (BASELINE configs[4]: Rabenseifner, 256 MiB float32 SUM, 9 ranks = 8 GPUs +
  * one idle spare, a single kill mid-exchange, ULFM-style shrink + recovery).
  *
- *   ftrun -np N --devmap d0,d1,... ftbench <raben|rd> <count> <calls>
+ *   ftrun -np N --devmap d0,d1,... ftbench <raben|rd> <count> <calls> [f32|f16|bf16]
+ *
+ * The element type is float32 unless the 4th argument or FTBENCH_DTYPE names another (the
+ * argument wins): float16 and bfloat16 time the same job on 2-byte elements.  Their inputs are
+ * small integers whose sums stay exact in 8 significand bits -- the rank modulo 4, or with
+ * FTBENCH_PATTERN (7 i + 13 r) mod 4 -- so that at up to 64 ranks every partial sum is an
+ * integer below 256: finite, and the same in any reduction tree.
  *
  * Every rank hipMallocs float32 send / receive vectors of `count` elements on its device,
  * fills the send vector with its original rank (the reference drivers' input,
@@ -35,16 +41,60 @@
         }                                                                                          \
     } while (0)
 
+/* float32 -> the 16-bit formats and back, for integers of at most 8 significand bits (exact:
+ * nothing to round, no subnormals) */
+static uint16_t to_bf16(float v)
+{
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    return (uint16_t)(u >> 16);
+}
+static float from_bf16(uint16_t h)
+{
+    uint32_t u = (uint32_t)h << 16;
+    float v;
+    memcpy(&v, &u, 4);
+    return v;
+}
+static uint16_t to_f16(float v)
+{
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    if ((u & 0x7fffffffu) == 0) return (uint16_t)(u >> 16);
+    return (uint16_t)(((u >> 16) & 0x8000u) | ((((u >> 23) & 0xffu) - 127 + 15) << 10) | ((u >> 13) & 0x3ffu));
+}
+static float from_f16(uint16_t h)
+{
+    uint32_t u = (uint32_t)(h & 0x8000u) << 16;
+    if (h & 0x7fffu) u |= ((((uint32_t)h >> 10) & 0x1fu) - 15 + 127) << 23 | ((uint32_t)h & 0x3ffu) << 13;
+    float v;
+    memcpy(&v, &u, 4);
+    return v;
+}
+
+/* the 16-bit job: same schedule calls, same JSON line */
+static int run16(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev);
+
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: ftbench <raben|rd> <count> <calls>\n");
+        fprintf(stderr, "usage: ftbench <raben|rd> <count> <calls> [f32|f16|bf16]\n");
         return 2;
     }
     int rd = !strcmp(argv[1], "rd");
     size_t count = strtoull(argv[2], NULL, 10);
     int calls = atoi(argv[3]);
     if (count == 0 || calls < 1 || calls > MAX_CALLS) return 2;
+    const char *tn = argc > 4 ? argv[4] : getenv("FTBENCH_DTYPE");
+    int dt16 = 0;
+    if (tn && *tn && strcmp(tn, "f32")) {
+        if (!strcmp(tn, "f16")) dt16 = FTAR_FLOAT16;
+        else if (!strcmp(tn, "bf16")) dt16 = FTAR_BFLOAT16;
+        else {
+            fprintf(stderr, "ftbench: element type %s is not f32, f16 or bf16\n", tn);
+            return 2;
+        }
+    }
 
     ftar_comm *comm;
     if (ftar_init(&comm) != FTAR_SUCCESS) return 3;
@@ -53,6 +103,7 @@ int main(int argc, char **argv)
     ftar_world_size(comm, &wsize);
     ftar_comm_device(comm, &dev);
     CHECK_HIP(hipSetDevice(dev));
+    if (dt16) return run16(rd, count, calls, (ftar_dtype)dt16, comm, wrank, wsize, dev);
 
     /* FTBENCH_PATTERN=1: x_r[i] = (7 i + 13 r) mod 4096 instead of r, so every element
      * has its own exact sum (all partial sums are integers < 2^24) and a misplaced
@@ -92,6 +143,67 @@ int main(int argc, char **argv)
                 size_t sum = 0;
                 for (int q = 0; q < members; q++) sum += (7 * i + 13 * (size_t)q) % 4096;
                 want = (float)sum;
+            }
+            if (h[i] != want) {
+                uniform[c] = 0;
+                break;
+            }
+        }
+    }
+    printf("{\"rank\": %d, \"size\": %d, \"device\": %d, \"step0_copy\": %d, \"calls\": [", wrank, wsize, dev,
+           step0_copy);
+    for (int c = 0; c < calls; c++)
+        printf("%s{\"rc\": %d, \"ms\": %.4f, \"recoveries\": %d, \"comm_size\": %d, \"value\": %.1f, \"uniform\": %s, "
+               "\"hbm_bytes\": %.0f}",
+               c ? ", " : "", rc[c], ms[c], rec[c], size_after[c], value[c], uniform[c] ? "true" : "false", hbm[c]);
+    printf("]}\n");
+    fflush(stdout);
+    ftar_finalize(comm);
+    (void)hipFree(s);
+    (void)hipFree(r);
+    free(h);
+    return 0;
+}
+
+static int run16(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev)
+{
+    const char *pe = getenv("FTBENCH_PATTERN");
+    const int pattern = pe && atoi(pe) != 0;
+    const int bf = dt == FTAR_BFLOAT16;
+    uint16_t *h = malloc(count * sizeof(uint16_t));
+    if (!h) return 4;
+    for (size_t i = 0; i < count; i++) {
+        const float v = pattern ? (float)((7 * i + 13 * (size_t)wrank) % 4) : (float)(wrank % 4);
+        h[i] = bf ? to_bf16(v) : to_f16(v);
+    }
+    uint16_t *s = NULL, *r = NULL;
+    CHECK_HIP(hipMalloc((void **)&s, count * sizeof(uint16_t)));
+    CHECK_HIP(hipMalloc((void **)&r, count * sizeof(uint16_t)));
+    CHECK_HIP(hipMemcpy(s, h, count * sizeof(uint16_t), hipMemcpyHostToDevice));
+    CHECK_HIP(hipDeviceSynchronize());
+
+    double ms[MAX_CALLS], value[MAX_CALLS], hbm[MAX_CALLS];
+    int rc[MAX_CALLS], rec[MAX_CALLS], size_after[MAX_CALLS], uniform[MAX_CALLS], step0_copy = 0;
+    for (int c = 0; c < calls; c++) {
+        rc[c] = rd ? ftar_recursive_doubling(s, r, count, dt, FTAR_SUM, comm)
+                   : ftar_allreduce_rabenseifner(s, r, count, dt, FTAR_SUM, comm);
+        ftar_stats st;
+        ftar_last_stats(comm, &st);
+        ms[c] = st.wall_s * 1e3;
+        hbm[c] = st.hbm_bytes;
+        rec[c] = st.recoveries;
+        size_after[c] = st.comm_size_after;
+        step0_copy |= st.step0_copy;
+        CHECK_HIP(hipMemcpy(h, r, count * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        value[c] = bf ? from_bf16(h[0]) : from_f16(h[0]);
+        uniform[c] = 1;
+        const int members = size_after[c];
+        for (size_t i = 0; i < count; i++) {
+            uint16_t want = h[0];
+            if (pattern) {
+                size_t sum = 0;
+                for (int q = 0; q < members; q++) sum += (7 * i + 13 * (size_t)q) % 4;
+                want = bf ? to_bf16((float)sum) : to_f16((float)sum);
             }
             if (h[i] != want) {
                 uniform[c] = 0;

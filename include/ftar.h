@@ -48,7 +48,21 @@ typedef enum {
     FTAR_INT32 = 0,   /* MPI_INT (the only type the reference drivers use) */
     FTAR_FLOAT32 = 1, /* north-star type */
     FTAR_INT64 = 2,
-    FTAR_FLOAT64 = 3
+    FTAR_FLOAT64 = 3,
+    /* The 2-byte float types (IEEE binary16 and bfloat16).  Every other value, 4..15 and
+     * 18.. included, is FTAR_ERR_ARG; like the other float types they have SUM, PROD, MAX
+     * and MIN only (FTAR_LAND..FTAR_BXOR: FTAR_ERR_OP).
+     *   SUM / PROD  one correctly rounded IEEE operation per combination in the element's own
+     *               format: round to nearest even, subnormals kept, overflow to +-inf, a NaN
+     *               operand gives some quiet NaN (payload unspecified).  The rounding happens
+     *               at every node of the schedule's reduction tree, so every form of a
+     *               schedule and every recovery replay gives the same bits, as for float32;
+     *               nothing accumulates in a wider type.
+     *   MAX / MIN   (x > y) ? x : y and (x < y) ? x : y with the operand roles of the other
+     *               types: the result is one of the two operands bit for bit, also for +-0
+     *               and NaN. */
+    FTAR_FLOAT16 = 16,
+    FTAR_BFLOAT16 = 17
 } ftar_dtype;
 
 /* MPI's predefined reduction ops (MAXLOC / MINLOC need pair types and are not offered).
