@@ -22,7 +22,10 @@ LIB_PATH = os.path.join(HERE, "lib", "libftar.so")
 
 INT32, FLOAT32, INT64, FLOAT64 = 0, 1, 2, 3
 FLOAT16, BFLOAT16 = 16, 17  # 2-byte floats: SUM / PROD / MAX / MIN, rounded in their own format at every combination
+# MPI's pair types (value, index) for MAXLOC / MINLOC; torch has no such dtype: pack_pairs / unpack_pairs
+FLOAT_INT, TWO_INT, DOUBLE_INT = 32, 33, 34
 SUM, PROD, MAX, MIN = 0, 1, 2, 3
+MAXLOC, MINLOC = 16, 17  # the pair types' only ops: the winning (value, index) copied whole, ties to the lower index
 LAND, BAND, LOR, BOR, LXOR, BXOR = 4, 5, 6, 7, 8, 9  # MPI logical / bitwise ops (integer types)
 PH_PRE, PH_LOOP, PH_AG, PH_POST = 0, 1, 2, 3
 PT_BEFORE, PT_AFTER, PT_BARRIER, PT_DURING = 0, 1, 2, 3
@@ -36,7 +39,7 @@ OPT_GATE_MAX = 12
 OPT_MESH_WAIT = 13
 REDUNDANCY_NEVER, REDUNDANCY_ALWAYS, REDUNDANCY_AUTO = 0, 1, 2  # OPT_REDUNDANCY values
 SUCCESS, ERR_ARG, ERR_UNKNOWN, ERR_OTHER, ERR_PROC_FAILED = 0, 13, 14, 16, 75
-ERR_OP = 9  # MPI_ERR_OP: a logical / bitwise op on a float type
+ERR_OP = 9  # MPI_ERR_OP: an op the element type does not have
 
 
 class FtarError(RuntimeError):
@@ -136,6 +139,50 @@ def _dtype_of(t) -> int:
     if t.dtype not in m:
         raise FtarError(f"unsupported dtype {t.dtype}")
     return m[t.dtype]
+
+
+def _pair_value_dtype(dtype: int):
+    import torch
+    m = {FLOAT_INT: torch.float32, TWO_INT: torch.int32, DOUBLE_INT: torch.float64}
+    if dtype not in m:
+        raise FtarError(f"dtype {dtype} is not a pair type")
+    return m[dtype]
+
+
+def pack_pairs(values, indices, dtype: int):
+    """The (value, index) pairs of a pair type as one contiguous tensor on the values' device, to
+    pass with count = n and dtype = `dtype`: (n, 2) int32 for FLOAT_INT / TWO_INT (value bits,
+    index), (n, 2) int64 for DOUBLE_INT (value bits; the index in the low 4 bytes of the second
+    word, the padding zero).  `values` must have the type's value dtype (float32, int32,
+    float64); `indices` any integer tensor of values that fit int32."""
+    import torch
+    vt = _pair_value_dtype(dtype)
+    if values.dtype != vt or values.dim() != 1 or indices.shape != values.shape or indices.dtype.is_floating_point:
+        raise FtarError(f"pack_pairs: values must be 1-D {vt}, indices integers of the same shape")
+    idx = indices.to(device=values.device, dtype=torch.int32)
+    if dtype == DOUBLE_INT:
+        out = torch.zeros((values.numel(), 4), dtype=torch.int32, device=values.device)
+        out[:, 0:2] = values.contiguous().view(torch.int32).view(-1, 2)
+        out[:, 2] = idx
+        return out.view(torch.int64)
+    out = torch.empty((values.numel(), 2), dtype=torch.int32, device=values.device)
+    out[:, 0] = values.contiguous().view(torch.int32)
+    out[:, 1] = idx
+    return out
+
+
+def unpack_pairs(t, dtype: int):
+    """(values, indices) of a tensor laid out as pack_pairs does: values in the type's value
+    dtype bit for bit, indices int32."""
+    import torch
+    vt = _pair_value_dtype(dtype)
+    want = torch.int64 if dtype == DOUBLE_INT else torch.int32
+    if t.dtype != want or t.dim() != 2 or t.shape[1] != 2 or not t.is_contiguous():
+        raise FtarError(f"unpack_pairs: expected a contiguous (n, 2) {want} tensor")
+    w = t.view(torch.int32)
+    if dtype == DOUBLE_INT:
+        return w[:, 0:2].contiguous().view(torch.float64).view(-1), w[:, 2].clone()
+    return w[:, 0].contiguous().view(vt), w[:, 1].clone()
 
 
 def _ptr(x):

@@ -38,6 +38,9 @@ size_t ftar_esize(int dtype)
     case FTAR_FLOAT16:
     case FTAR_BFLOAT16: /* only where the device layer has them (ftar_dev.h) */
         return (fdev_has_dtype && fdev_has_dtype(dtype)) ? 2 : 0;
+    case FTAR_FLOAT_INT:
+    case FTAR_2INT: return (fdev_has_dtype && fdev_has_dtype(dtype)) ? 8 : 0;
+    case FTAR_DOUBLE_INT: return (fdev_has_dtype && fdev_has_dtype(dtype)) ? 16 : 0;
     default: return 0;
     }
 }
@@ -47,11 +50,19 @@ static int is_float_type(int dtype)
     return dtype == FTAR_FLOAT32 || dtype == FTAR_FLOAT64 || dtype == FTAR_FLOAT16 || dtype == FTAR_BFLOAT16;
 }
 
+static int is_pair_type(int dtype)
+{
+    return dtype == FTAR_FLOAT_INT || dtype == FTAR_2INT || dtype == FTAR_DOUBLE_INT;
+}
+
 /* MPI_Reduce_local's type/op check: an unknown type or op is an argument error, a
- * logical or bitwise op on a floating-point type is MPI_ERR_OP (MPI 4.1, 6.9.2). */
+ * logical or bitwise op on a floating-point type is MPI_ERR_OP (MPI 4.1, 6.9.2), and so is
+ * MAXLOC / MINLOC on anything but a pair type or any other op on a pair type (6.9.4). */
 int ftar_check_op(int dtype, int op)
 {
-    if (ftar_esize(dtype) == 0 || op < FTAR_SUM || op >= FTAR_NOPS) return FTAR_ERR_ARG;
+    const int loc = op == FTAR_MAXLOC || op == FTAR_MINLOC;
+    if (ftar_esize(dtype) == 0 || op < FTAR_SUM || (op >= FTAR_NOPS && !loc)) return FTAR_ERR_ARG;
+    if (is_pair_type(dtype) != loc) return FTAR_ERR_OP;
     if (op >= FTAR_LAND && is_float_type(dtype)) return FTAR_ERR_OP;
     return FTAR_SUCCESS;
 }

@@ -225,7 +225,8 @@ int fdev_set_reduce_variant(int v);
 
 /* 1 if the device layer has kernels for element type `dtype`.  Weak: a device layer that
  * does not define it (the host-sim test layer) has the four original types only, and the
- * shared host C then refuses the 2-byte float types at the boundary (ftar_esize). */
+ * shared host C then refuses the 2-byte float types and the pair types at the boundary
+ * (ftar_esize). */
 int fdev_has_dtype(int dtype) __attribute__((weak));
 
 const char *fdev_last_error(void);

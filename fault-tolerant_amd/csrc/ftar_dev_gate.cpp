@@ -241,7 +241,7 @@ int fdev_run_gated(ftar_dev *d, int dtype, int op, const fdev_seg *segs, int nse
 {
     *gated = 0;
     size_t es = esize_of(dtype);
-    if (es == 0 || op < 0 || op >= ftar::kNumOps || nseg < 0 || nseg > FDEV_MAX_SEGS || tag < 0 || tag >= FDEV_NTAGS) {
+    if (es == 0 || !ftar::op_known(op) || nseg < 0 || nseg > FDEV_MAX_SEGS || tag < 0 || tag >= FDEV_NTAGS) {
         snprintf(g_err, sizeof(g_err), "fdev_run_gated: bad arguments");
         return 13;
     }

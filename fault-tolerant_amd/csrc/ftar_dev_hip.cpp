@@ -73,7 +73,10 @@ size_t esize_of(int dtype)
     case ftar::kInt32:
     case ftar::kFloat32: return 4;
     case ftar::kInt64:
-    case ftar::kFloat64: return 8;
+    case ftar::kFloat64:
+    case ftar::kFloatInt:
+    case ftar::k2Int: return 8;
+    case ftar::kDoubleInt: return 16;
     default: return 0;
     }
 }
@@ -515,7 +518,7 @@ int fdev_has_dtype(int dtype) { return esize_of(dtype) != 0; }
 int fdev_reduce_local(const void *in, void *inout, size_t n, int dtype, int op, void *stream)
 {
     size_t es = esize_of(dtype);
-    if (es == 0 || op < 0 || op >= ftar::kNumOps) {
+    if (es == 0 || !ftar::op_known(op)) {
         snprintf(g_err, sizeof(g_err), "reduce_local: bad dtype/op");
         return 13;
     }

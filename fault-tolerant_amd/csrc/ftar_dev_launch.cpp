@@ -109,7 +109,7 @@ bool overlaps(const void *a, size_t na, const void *b, size_t nb)
 int run_on(ftar_dev *d, hipStream_t st, int dtype, int op, const fdev_seg *segs, int nseg, int tag)
 {
     size_t es = esize_of(dtype);
-    if (es == 0 || op < 0 || op >= ftar::kNumOps || nseg < 0 || nseg > FDEV_MAX_SEGS || tag < 0 || tag >= FDEV_NTAGS) {
+    if (es == 0 || !ftar::op_known(op) || nseg < 0 || nseg > FDEV_MAX_SEGS || tag < 0 || tag >= FDEV_NTAGS) {
         snprintf(g_err, sizeof(g_err), "fdev_run: bad arguments");
         return 13;
     }
@@ -170,7 +170,7 @@ int fdev_tree_out(ftar_dev *d, int dtype, int op, const void *const *src, int ns
                   void *const *more, int nmore, int more_remote, size_t n, int tag)
 {
     size_t es = esize_of(dtype);
-    if (es == 0 || op < 0 || op >= ftar::kNumOps || tag < 0 || tag >= FDEV_NTAGS ||
+    if (es == 0 || !ftar::op_known(op) || tag < 0 || tag >= FDEV_NTAGS ||
         !(nsrc == 2 || nsrc == 4 || nsrc == 8 || nsrc == 16) || nmore < 0 || nmore > ftar::kMaxMore) {
         snprintf(g_err, sizeof(g_err), "fdev_tree: bad arguments");
         return 13;
@@ -233,7 +233,7 @@ int build_batch(ftar_dev *d, int dtype, int op, const void *const *src, int nsrc
                 double *link, double *hbm)
 {
     size_t es = esize_of(dtype);
-    if (es == 0 || op < 0 || op >= ftar::kNumOps || tag < 0 || tag >= FDEV_NTAGS || ntree < 1 || ntree > ftar::kMaxBatch ||
+    if (es == 0 || !ftar::op_known(op) || tag < 0 || tag >= FDEV_NTAGS || ntree < 1 || ntree > ftar::kMaxBatch ||
         !(nsrc == 2 || nsrc == 4 || nsrc == 8)) {
         snprintf(g_err, sizeof(g_err), "fdev_tree_batch: bad arguments");
         return 13;

@@ -6,9 +6,17 @@
 
 namespace ftar {
 
-enum { kInt32 = 0, kFloat32 = 1, kInt64 = 2, kFloat64 = 3, kFloat16 = 16, kBFloat16 = 17 };
-enum { kSum = 0, kProd = 1, kMax = 2, kMin = 3, kLand = 4, kBand = 5, kLor = 6, kBor = 7, kLxor = 8, kBxor = 9 };
+enum {
+    kInt32 = 0, kFloat32 = 1, kInt64 = 2, kFloat64 = 3, kFloat16 = 16, kBFloat16 = 17,
+    kFloatInt = 32, k2Int = 33, kDoubleInt = 34 // MPI's pair types: 8, 8 and 16 bytes, kMaxloc / kMinloc only
+};
+enum {
+    kSum = 0, kProd = 1, kMax = 2, kMin = 3, kLand = 4, kBand = 5, kLor = 6, kBor = 7, kLxor = 8, kBxor = 9,
+    kMaxloc = 16, kMinloc = 17
+};
 constexpr int kNumOps = 10; // logical / bitwise ops (>= kLand) exist for the integer types only
+// an op some element type has (which types: with_op in ftar_kernels.hip)
+inline bool op_known(int op) { return (op >= 0 && op < kNumOps) || op == kMaxloc || op == kMinloc; }
 enum { kCopy = 0, kReduce = 1 };
 
 constexpr int kMaxKSegs = 48; // 16 user segments x (head, body, tail); 2.3 KB of kernarg

@@ -107,32 +107,73 @@ template <> __device__ __forceinline__ bf16_t apply<bf16_t, kProd>(bf16_t x, bf1
 template <> __device__ __forceinline__ bf16_t apply<bf16_t, kMax>(bf16_t x, bf16_t y) { return apply_bf16<kMax>(x, y); }
 template <> __device__ __forceinline__ bf16_t apply<bf16_t, kMin>(bf16_t x, bf16_t y) { return apply_bf16<kMin>(x, y); }
 
+// MPI's pair types (value, index): plain element structs of 8, 8 and 16 bytes with the
+// alignment of their C layout (4, 4, 8), the 16-byte one with its padding named so that a copy
+// of the struct carries it.  MAXLOC / MINLOC only: compare-and-select of whole elements.
+struct fi_t { float v; int32_t i; };
+struct ii_t { int32_t v; int32_t i; };
+struct di_t { double v; int32_t i; uint32_t pad; };
+static_assert(sizeof(fi_t) == 8 && alignof(fi_t) == 4 && sizeof(ii_t) == 8 && alignof(ii_t) == 4, "8-byte pairs");
+static_assert(sizeof(di_t) == 16 && alignof(di_t) == 8, "MPI_DOUBLE_INT, LP64");
+template <typename T> struct is_pair : std::false_type {};
+template <> struct is_pair<fi_t> : std::true_type {};
+template <> struct is_pair<ii_t> : std::true_type {};
+template <> struct is_pair<di_t> : std::true_type {};
+
+// x wins: the larger (MAXLOC) or smaller (MINLOC) value, an equal value with the lower index.
+// A NaN value fails every comparison: y.  The three compares are combined as lane masks (| and
+// &, not || and &&: nothing to short-circuit, and no branch around a compare).
+template <int OP, typename V>
+__device__ __forceinline__ bool loc_takes_x(V xv, int32_t xi, V yv, int32_t yi)
+{
+    static_assert(OP == kMaxloc || OP == kMinloc, "pair types have MAXLOC / MINLOC only");
+    const bool better = OP == kMaxloc ? xv > yv : xv < yv;
+    return better | ((xv == yv) & (xi < yi));
+}
+#define FTAR_APPLY_LOC(T, OP)                                                                                  \
+    template <> __device__ __forceinline__ T apply<T, OP>(T x, T y) { return loc_takes_x<OP>(x.v, x.i, y.v, y.i) ? x : y; }
+FTAR_APPLY_LOC(fi_t, kMaxloc)
+FTAR_APPLY_LOC(fi_t, kMinloc)
+FTAR_APPLY_LOC(ii_t, kMaxloc)
+FTAR_APPLY_LOC(ii_t, kMinloc)
+FTAR_APPLY_LOC(di_t, kMaxloc)
+FTAR_APPLY_LOC(di_t, kMinloc)
+#undef FTAR_APPLY_LOC
+
 // Runs fn(std::integral_constant<int, OP>) for the runtime op: one instantiation per op
-// the element type has (the logical / bitwise ops only for the integer types).
+// the element type has (the logical / bitwise ops only for the integer types, MAXLOC /
+// MINLOC and nothing else for the pair types).
 template <typename T, typename Fn>
 static hipError_t with_op(int op, Fn &&fn)
 {
     using std::integral_constant;
-    constexpr bool integer = std::is_integral<T>::value;
-    switch (op) {
-    case kSum: return fn(integral_constant<int, kSum>{});
-    case kProd: return fn(integral_constant<int, kProd>{});
-    case kMax: return fn(integral_constant<int, kMax>{});
-    case kMin: return fn(integral_constant<int, kMin>{});
-    default: break;
-    }
-    if constexpr (integer) {
+    if constexpr (is_pair<T>::value) {
         switch (op) {
-        case kLand: return fn(integral_constant<int, kLand>{});
-        case kBand: return fn(integral_constant<int, kBand>{});
-        case kLor: return fn(integral_constant<int, kLor>{});
-        case kBor: return fn(integral_constant<int, kBor>{});
-        case kLxor: return fn(integral_constant<int, kLxor>{});
-        case kBxor: return fn(integral_constant<int, kBxor>{});
+        case kMaxloc: return fn(integral_constant<int, kMaxloc>{});
+        case kMinloc: return fn(integral_constant<int, kMinloc>{});
+        default: return hipErrorInvalidValue;
+        }
+    } else {
+        switch (op) {
+        case kSum: return fn(integral_constant<int, kSum>{});
+        case kProd: return fn(integral_constant<int, kProd>{});
+        case kMax: return fn(integral_constant<int, kMax>{});
+        case kMin: return fn(integral_constant<int, kMin>{});
         default: break;
         }
+        if constexpr (std::is_integral<T>::value) {
+            switch (op) {
+            case kLand: return fn(integral_constant<int, kLand>{});
+            case kBand: return fn(integral_constant<int, kBand>{});
+            case kLor: return fn(integral_constant<int, kLor>{});
+            case kBor: return fn(integral_constant<int, kBor>{});
+            case kLxor: return fn(integral_constant<int, kLxor>{});
+            case kBxor: return fn(integral_constant<int, kBxor>{});
+            default: break;
+            }
+        }
+        return hipErrorInvalidValue;
     }
-    return hipErrorInvalidValue;
 }
 
 template <typename T, int OP>
@@ -202,6 +243,37 @@ FTAR_APPLY16_PK(bf16_t, kMax)
 FTAR_APPLY16_PK(bf16_t, kMin)
 #undef FTAR_APPLY16_PK
 
+// The pair types' vector path: the compare reads the value and index dwords where they were
+// loaded, and every dword of the result is selected whole from a or b by it (v_cndmask_b32) --
+// two independent selects per vector for the 8-byte types, one for the 16-byte type, whose
+// padding dword travels like the others.
+__device__ __forceinline__ float pair_val(const fi_t *, uint32_t v) { return __builtin_bit_cast(float, v); }
+__device__ __forceinline__ int32_t pair_val(const ii_t *, uint32_t v) { return (int32_t)v; }
+#define FTAR_APPLY16_LOC8(T, OP)                                                                               \
+    template <> __device__ __forceinline__ uint4 apply16<T, OP>(uint4 a, uint4 b)                              \
+    {                                                                                                          \
+        constexpr const T *tag = nullptr;                                                                      \
+        const bool t0 = loc_takes_x<OP>(pair_val(tag, a.x), (int32_t)a.y, pair_val(tag, b.x), (int32_t)b.y);   \
+        const bool t1 = loc_takes_x<OP>(pair_val(tag, a.z), (int32_t)a.w, pair_val(tag, b.z), (int32_t)b.w);   \
+        return make_uint4(t0 ? a.x : b.x, t0 ? a.y : b.y, t1 ? a.z : b.z, t1 ? a.w : b.w);                     \
+    }
+FTAR_APPLY16_LOC8(fi_t, kMaxloc)
+FTAR_APPLY16_LOC8(fi_t, kMinloc)
+FTAR_APPLY16_LOC8(ii_t, kMaxloc)
+FTAR_APPLY16_LOC8(ii_t, kMinloc)
+#undef FTAR_APPLY16_LOC8
+#define FTAR_APPLY16_LOC16(OP)                                                                                 \
+    template <> __device__ __forceinline__ uint4 apply16<di_t, OP>(uint4 a, uint4 b)                           \
+    {                                                                                                          \
+        const double av = __builtin_bit_cast(double, (uint64_t)a.x | ((uint64_t)a.y << 32));                   \
+        const double bv = __builtin_bit_cast(double, (uint64_t)b.x | ((uint64_t)b.y << 32));                   \
+        const bool t = loc_takes_x<OP>(av, (int32_t)a.z, bv, (int32_t)b.z);                                    \
+        return make_uint4(t ? a.x : b.x, t ? a.y : b.y, t ? a.z : b.z, t ? a.w : b.w);                         \
+    }
+FTAR_APPLY16_LOC16(kMaxloc)
+FTAR_APPLY16_LOC16(kMinloc)
+#undef FTAR_APPLY16_LOC16
+
 // ---------------------------------------------------------------------------------
 // segment kernel
 // ---------------------------------------------------------------------------------
@@ -252,12 +324,12 @@ __device__ __forceinline__ void signal_acquire(const KSignal &G)
 // signal and the peers' barrier.  The grid is small (<= FTAR_FLAG_MAX_BLOCKS workgroups), so
 // every workgroup is resident while the others wait at the gate.
 template <typename E>
-__device__ __forceinline__ void stage_copy(const KSignal &G)
+__device__ __forceinline__ void stage_copy(const KSignal &G, size_t n)
 {
     const E *s = (const E *)G.stage_src;
     E *d = (E *)G.stage_dst;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < G.stage_n; i += stride) d[i] = s[i];
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) d[i] = s[i];
 }
 
 // 16-byte vectors when both ends are 16-byte aligned (the workspace and a hipMalloc'd input
@@ -270,7 +342,7 @@ __device__ __forceinline__ bool stage_copy_vec(const KSignal &G)
     uint4 *d = (uint4 *)G.stage_dst;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) d[i] = s[i];
-    const size_t done = nv * 16 / G.stage_es; // elements copied as vectors
+    const size_t done = nv * 16 / G.stage_es; // elements copied as vectors (all of them at 16 bytes each)
     if (blockIdx.x == 0)
         for (size_t i = done + threadIdx.x; i < G.stage_n; i += blockDim.x) {
             if (G.stage_es == 8) ((unsigned long long *)G.stage_dst)[i] = ((const unsigned long long *)G.stage_src)[i];
@@ -284,9 +356,10 @@ __device__ __forceinline__ void signal_stage(const KSignal &G)
 {
     if (!G.stage_dst) return;
     if (stage_copy_vec(G)) {
-    } else if (G.stage_es == 8) stage_copy<unsigned long long>(G);
-    else if (G.stage_es == 2) stage_copy<unsigned short>(G);
-    else stage_copy<unsigned>(G);
+    } else if (G.stage_es == 16) stage_copy<unsigned long long>(G, 2 * G.stage_n); // 8-byte aligned: two halves
+    else if (G.stage_es == 8) stage_copy<unsigned long long>(G, G.stage_n);
+    else if (G.stage_es == 2) stage_copy<unsigned short>(G, G.stage_n);
+    else stage_copy<unsigned>(G, G.stage_n);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -648,6 +721,9 @@ hipError_t launch_tree(int dtype, int op, int p, const TreeArgs &A, unsigned gri
     case kFloat64: return launch_tree_t<double>(op, p, A, grid, s);
     case kFloat16: return launch_tree_t<f16_t>(op, p, A, grid, s);
     case kBFloat16: return launch_tree_t<bf16_t>(op, p, A, grid, s);
+    case kFloatInt: return launch_tree_t<fi_t>(op, p, A, grid, s);
+    case k2Int: return launch_tree_t<ii_t>(op, p, A, grid, s);
+    case kDoubleInt: return launch_tree_t<di_t>(op, p, A, grid, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -721,6 +797,9 @@ hipError_t launch_tree_batch(int dtype, int op, int p, const TreeBatch &B, unsig
     case kFloat64: return launch_batch_t<double>(op, p, B, grid, s);
     case kFloat16: return launch_batch_t<f16_t>(op, p, B, grid, s);
     case kBFloat16: return launch_batch_t<bf16_t>(op, p, B, grid, s);
+    case kFloatInt: return launch_batch_t<fi_t>(op, p, B, grid, s);
+    case k2Int: return launch_batch_t<ii_t>(op, p, B, grid, s);
+    case kDoubleInt: return launch_batch_t<di_t>(op, p, B, grid, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -782,6 +861,9 @@ hipError_t launch_segments(int dtype, int op, const KSegList &L, unsigned grid, 
     case kFloat64: return launch_t<double>(op, L, grid, s);
     case kFloat16: return launch_t<f16_t>(op, L, grid, s);
     case kBFloat16: return launch_t<bf16_t>(op, L, grid, s);
+    case kFloatInt: return launch_t<fi_t>(op, L, grid, s);
+    case k2Int: return launch_t<ii_t>(op, L, grid, s);
+    case kDoubleInt: return launch_t<di_t>(op, L, grid, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -809,6 +891,9 @@ hipError_t launch_reduce_lds(int dtype, int op, void *inout, const void *in, siz
     case kFloat64: return launch_lds_t<double>(op, io, i, nvec, grid, s, nts);
     case kFloat16: return launch_lds_t<f16_t>(op, io, i, nvec, grid, s, nts);
     case kBFloat16: return launch_lds_t<bf16_t>(op, io, i, nvec, grid, s, nts);
+    case kFloatInt: return launch_lds_t<fi_t>(op, io, i, nvec, grid, s, nts);
+    case k2Int: return launch_lds_t<ii_t>(op, io, i, nvec, grid, s, nts);
+    case kDoubleInt: return launch_lds_t<di_t>(op, io, i, nvec, grid, s, nts);
     default: return hipErrorInvalidValue;
     }
 }

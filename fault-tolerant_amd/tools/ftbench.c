@@ -3,13 +3,17 @@
  * of bench.py (BASELINE configs[4]: Rabenseifner, 256 MiB float32 SUM, 9 ranks = 8 GPUs +
  * one idle spare, a single kill mid-exchange, ULFM-style shrink + recovery).
  *
- *   ftrun -np N --devmap d0,d1,... ftbench <raben|rd> <count> <calls> [f32|f16|bf16]
+ *   ftrun -np N --devmap d0,d1,... ftbench <raben|rd> <count> <calls> [f32|f16|bf16|float_int|2int|double_int]
  *
  * The element type is float32 unless the 4th argument or FTBENCH_DTYPE names another (the
  * argument wins): float16 and bfloat16 time the same job on 2-byte elements.  Their inputs are
  * small integers whose sums stay exact in 8 significand bits -- the rank modulo 4, or with
  * FTBENCH_PATTERN (7 i + 13 r) mod 4 -- so that at up to 64 ranks every partial sum is an
  * integer below 256: finite, and the same in any reduction tree.
+ * float_int, 2int and double_int time MAXLOC on MPI's pair types: every rank contributes the
+ * value f(rank, i) -- its rank, or with FTBENCH_PATTERN (7 i + 13 r) mod 3, which ties between
+ * ranks from 4 ranks on -- and its rank as the index; the check recomputes each element's winner
+ * (the largest value, the lowest rank among equals) on the host.
  *
  * Every rank hipMallocs float32 send / receive vectors of `count` elements on its device,
  * fills the send vector with its original rank (the reference drivers' input,
@@ -74,11 +78,13 @@ static float from_f16(uint16_t h)
 
 /* the 16-bit job: same schedule calls, same JSON line */
 static int run16(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev);
+/* the pair-type job (MAXLOC) */
+static int runpair(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev);
 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: ftbench <raben|rd> <count> <calls> [f32|f16|bf16]\n");
+        fprintf(stderr, "usage: ftbench <raben|rd> <count> <calls> [f32|f16|bf16|float_int|2int|double_int]\n");
         return 2;
     }
     int rd = !strcmp(argv[1], "rd");
@@ -86,12 +92,15 @@ int main(int argc, char **argv)
     int calls = atoi(argv[3]);
     if (count == 0 || calls < 1 || calls > MAX_CALLS) return 2;
     const char *tn = argc > 4 ? argv[4] : getenv("FTBENCH_DTYPE");
-    int dt16 = 0;
+    int dt16 = 0, dtpair = 0;
     if (tn && *tn && strcmp(tn, "f32")) {
         if (!strcmp(tn, "f16")) dt16 = FTAR_FLOAT16;
         else if (!strcmp(tn, "bf16")) dt16 = FTAR_BFLOAT16;
+        else if (!strcmp(tn, "float_int")) dtpair = FTAR_FLOAT_INT;
+        else if (!strcmp(tn, "2int")) dtpair = FTAR_2INT;
+        else if (!strcmp(tn, "double_int")) dtpair = FTAR_DOUBLE_INT;
         else {
-            fprintf(stderr, "ftbench: element type %s is not f32, f16 or bf16\n", tn);
+            fprintf(stderr, "ftbench: element type %s is not f32, f16, bf16, float_int, 2int or double_int\n", tn);
             return 2;
         }
     }
@@ -104,6 +113,7 @@ int main(int argc, char **argv)
     ftar_comm_device(comm, &dev);
     CHECK_HIP(hipSetDevice(dev));
     if (dt16) return run16(rd, count, calls, (ftar_dtype)dt16, comm, wrank, wsize, dev);
+    if (dtpair) return runpair(rd, count, calls, (ftar_dtype)dtpair, comm, wrank, wsize, dev);
 
     /* FTBENCH_PATTERN=1: x_r[i] = (7 i + 13 r) mod 4096 instead of r, so every element
      * has its own exact sum (all partial sums are integers < 2^24) and a misplaced
@@ -217,6 +227,83 @@ static int run16(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm
         printf("%s{\"rc\": %d, \"ms\": %.4f, \"recoveries\": %d, \"comm_size\": %d, \"value\": %.1f, \"uniform\": %s, "
                "\"hbm_bytes\": %.0f}",
                c ? ", " : "", rc[c], ms[c], rec[c], size_after[c], value[c], uniform[c] ? "true" : "false", hbm[c]);
+    printf("]}\n");
+    fflush(stdout);
+    ftar_finalize(comm);
+    (void)hipFree(s);
+    (void)hipFree(r);
+    free(h);
+    return 0;
+}
+
+/* rank q's contribution to element i: the value (a small integer, exact in every value type) */
+static int pair_value(int pattern, size_t i, int q) { return pattern ? (int)((7 * i + 13 * (size_t)q) % 3) : q; }
+
+static void pair_put(void *buf, ftar_dtype dt, size_t i, int v, int idx)
+{
+    if (dt == FTAR_FLOAT_INT) ((ftar_float_int *)buf)[i] = (ftar_float_int){(float)v, idx};
+    else if (dt == FTAR_2INT) ((ftar_2int *)buf)[i] = (ftar_2int){v, idx};
+    else ((ftar_double_int *)buf)[i] = (ftar_double_int){(double)v, idx};
+}
+
+static void pair_get(const void *buf, ftar_dtype dt, size_t i, double *v, int *idx)
+{
+    if (dt == FTAR_FLOAT_INT) *v = ((const ftar_float_int *)buf)[i].v, *idx = ((const ftar_float_int *)buf)[i].i;
+    else if (dt == FTAR_2INT) *v = ((const ftar_2int *)buf)[i].v, *idx = ((const ftar_2int *)buf)[i].i;
+    else *v = ((const ftar_double_int *)buf)[i].v, *idx = ((const ftar_double_int *)buf)[i].i;
+}
+
+static int runpair(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev)
+{
+    const char *pe = getenv("FTBENCH_PATTERN");
+    const int pattern = pe && atoi(pe) != 0;
+    const size_t es = dt == FTAR_DOUBLE_INT ? sizeof(ftar_double_int) : sizeof(ftar_2int);
+    void *h = calloc(count, es); /* (zeroed: the padding of ftar_double_int too) */
+    if (!h) return 4;
+    for (size_t i = 0; i < count; i++) pair_put(h, dt, i, pair_value(pattern, i, wrank), wrank);
+    void *s = NULL, *r = NULL;
+    CHECK_HIP(hipMalloc(&s, count * es));
+    CHECK_HIP(hipMalloc(&r, count * es));
+    CHECK_HIP(hipMemcpy(s, h, count * es, hipMemcpyHostToDevice));
+    CHECK_HIP(hipDeviceSynchronize());
+
+    double ms[MAX_CALLS], value[MAX_CALLS], hbm[MAX_CALLS];
+    int rc[MAX_CALLS], rec[MAX_CALLS], size_after[MAX_CALLS], uniform[MAX_CALLS], index[MAX_CALLS], step0_copy = 0;
+    for (int c = 0; c < calls; c++) {
+        rc[c] = rd ? ftar_recursive_doubling(s, r, count, dt, FTAR_MAXLOC, comm)
+                   : ftar_allreduce_rabenseifner(s, r, count, dt, FTAR_MAXLOC, comm);
+        ftar_stats st;
+        ftar_last_stats(comm, &st);
+        ms[c] = st.wall_s * 1e3;
+        hbm[c] = st.hbm_bytes;
+        rec[c] = st.recoveries;
+        size_after[c] = st.comm_size_after;
+        step0_copy |= st.step0_copy;
+        CHECK_HIP(hipMemcpy(h, r, count * es, hipMemcpyDeviceToHost));
+        pair_get(h, dt, 0, &value[c], &index[c]);
+        uniform[c] = 1;
+        const int members = size_after[c]; /* the original ranks 0 .. members-1 (no fault) */
+        for (size_t i = 0; i < count; i++) {
+            /* the winner over the members: the largest value, the lowest rank among equals */
+            int wv = pair_value(pattern, i, 0), wi = 0;
+            for (int q = 1; q < members; q++)
+                if (pair_value(pattern, i, q) > wv) wv = pair_value(pattern, i, q), wi = q;
+            double v;
+            int idx;
+            pair_get(h, dt, i, &v, &idx);
+            if (v != (double)wv || idx != wi) {
+                uniform[c] = 0;
+                break;
+            }
+        }
+    }
+    printf("{\"rank\": %d, \"size\": %d, \"device\": %d, \"step0_copy\": %d, \"calls\": [", wrank, wsize, dev,
+           step0_copy);
+    for (int c = 0; c < calls; c++)
+        printf("%s{\"rc\": %d, \"ms\": %.4f, \"recoveries\": %d, \"comm_size\": %d, \"value\": %.1f, \"index\": %d, "
+               "\"uniform\": %s, \"hbm_bytes\": %.0f}",
+               c ? ", " : "", rc[c], ms[c], rec[c], size_after[c], value[c], index[c], uniform[c] ? "true" : "false",
+               hbm[c]);
     printf("]}\n");
     fflush(stdout);
     ftar_finalize(comm);

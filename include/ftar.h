@@ -34,7 +34,7 @@ extern "C" {
 
 /* ---- return codes: the MPI error classes the reference relies on ---------- */
 #define FTAR_SUCCESS         0   /* MPI_SUCCESS */
-#define FTAR_ERR_OP          9   /* MPI_ERR_OP: a bitwise / logical op on a floating-point type */
+#define FTAR_ERR_OP          9   /* MPI_ERR_OP: an op the element type does not have (ftar_op) */
 #define FTAR_ERR_ARG         13  /* MPI_ERR_ARG      (raben/rabenseifner.c:18-20) */
 #define FTAR_ERR_UNKNOWN     14  /* MPI_ERR_UNKNOWN  (raben/util.c:40-43) */
 #define FTAR_ERR_OTHER       16  /* MPI_ERR_OTHER    (rd/util.c:75) */
@@ -49,8 +49,8 @@ typedef enum {
     FTAR_FLOAT32 = 1, /* north-star type */
     FTAR_INT64 = 2,
     FTAR_FLOAT64 = 3,
-    /* The 2-byte float types (IEEE binary16 and bfloat16).  Every other value, 4..15 and
-     * 18.. included, is FTAR_ERR_ARG; like the other float types they have SUM, PROD, MAX
+    /* The 2-byte float types (IEEE binary16 and bfloat16).  Every value not listed here, 4..15,
+     * 18..31 and 35.. included, is FTAR_ERR_ARG; like the other float types they have SUM, PROD, MAX
      * and MIN only (FTAR_LAND..FTAR_BXOR: FTAR_ERR_OP).
      *   SUM / PROD  one correctly rounded IEEE operation per combination in the element's own
      *               format: round to nearest even, subnormals kept, overflow to +-inf, a NaN
@@ -62,10 +62,20 @@ typedef enum {
      *               types: the result is one of the two operands bit for bit, also for +-0
      *               and NaN. */
     FTAR_FLOAT16 = 16,
-    FTAR_BFLOAT16 = 17
+    FTAR_BFLOAT16 = 17,
+    /* MPI's pair types (value, index), laid out as the C structs below: the element types of
+     * FTAR_MAXLOC / FTAR_MINLOC and of nothing else (any op 0..9 on them: FTAR_ERR_OP, as
+     * MAXLOC / MINLOC on any other type).  Buffers need the struct's alignment only (4, 4, 8). */
+    FTAR_FLOAT_INT = 32,  /* MPI_FLOAT_INT:  ftar_float_int,  8 bytes */
+    FTAR_2INT = 33,       /* MPI_2INT:       ftar_2int,       8 bytes */
+    FTAR_DOUBLE_INT = 34  /* MPI_DOUBLE_INT: ftar_double_int, 16 bytes (LP64 C layout: 4 bytes of padding) */
 } ftar_dtype;
 
-/* MPI's predefined reduction ops (MAXLOC / MINLOC need pair types and are not offered).
+typedef struct { float v; int32_t i; } ftar_float_int;
+typedef struct { int32_t v; int32_t i; } ftar_2int;
+typedef struct { double v; int32_t i; /* 4 bytes of padding */ } ftar_double_int;
+
+/* MPI's predefined reduction ops, MAXLOC / MINLOC on the pair types included.
  * The reference passes its MPI_Op straight to MPI_Reduce_local (raben/rabenseifner.c:
  * 86-87,117,234-236; rd/util.c:32; rd/recursive_doubling.c:44,48), so every op MPI
  * defines for these types is valid there.  As in MPI, the logical and bitwise ops are
@@ -81,9 +91,19 @@ typedef enum {
     FTAR_LOR = 6,  /* MPI_LOR */
     FTAR_BOR = 7,  /* MPI_BOR */
     FTAR_LXOR = 8, /* MPI_LXOR: (a != 0) != (b != 0) */
-    FTAR_BXOR = 9  /* MPI_BXOR */
+    FTAR_BXOR = 9, /* MPI_BXOR */
+    /* 10..15: FTAR_ERR_ARG.  The pair types' two ops, with x and y in the operand roles of
+     * MAX / MIN:
+     *   MAXLOC  x if x.v > y.v || (x.v == y.v && x.i < y.i), otherwise y
+     *   MINLOC  x if x.v < y.v || (x.v == y.v && x.i < y.i), otherwise y
+     * The result is one of the two operands copied whole, bit for bit -- all 16 bytes of an
+     * ftar_double_int, padding included.  Equal values (+0 and -0 compare equal) go to the
+     * lower index; a NaN value makes both comparisons false, so y is returned.  Nothing is
+     * computed, so every form of a schedule and every recovery replay gives the same bits. */
+    FTAR_MAXLOC = 16, /* MPI_MAXLOC */
+    FTAR_MINLOC = 17  /* MPI_MINLOC */
 } ftar_op;
-#define FTAR_NOPS 10
+#define FTAR_NOPS 10 /* the ops 0..9 of the arithmetic types; MAXLOC / MINLOC lie outside */
 
 /* ---- deterministic fault injection --------------------------------------
  * A kill names the victim (original world rank) and the place in the schedule
