@@ -40,6 +40,8 @@ OPT_MESH_WAIT = 13
 REDUNDANCY_NEVER, REDUNDANCY_ALWAYS, REDUNDANCY_AUTO = 0, 1, 2  # OPT_REDUNDANCY values
 SUCCESS, ERR_ARG, ERR_UNKNOWN, ERR_OTHER, ERR_PROC_FAILED = 0, 13, 14, 16, 75
 ERR_OP = 9  # MPI_ERR_OP: an op the element type does not have
+ALGO_RD, ALGO_RABENSEIFNER = 0, 1  # ftar_algo: the schedule of allreduce_multi
+MULTI_MAX = 1024  # FTAR_MULTI_MAX: most buffers of one allreduce_multi call
 
 
 class FtarError(RuntimeError):
@@ -56,7 +58,8 @@ class Stats(ctypes.Structure):
                 ("mesh_steps", ctypes.c_int), ("export_retries", ctypes.c_int),
                 ("gated_launches", ctypes.c_int), ("gated_skips", ctypes.c_int),
                 ("user_stream_waits", ctypes.c_int), ("step0_copy", ctypes.c_int), ("gate_holds", ctypes.c_int),
-                ("gate_relaunches", ctypes.c_int), ("peer_waits", ctypes.c_int), ("peer_wait_skips", ctypes.c_int)]
+                ("gate_relaunches", ctypes.c_int), ("peer_waits", ctypes.c_int), ("peer_wait_skips", ctypes.c_int),
+                ("coalesced", ctypes.c_int)]
 
 
 class Kill(ctypes.Structure):
@@ -113,6 +116,7 @@ def lib():
         "ftar_recursive_doubling": ([vp, vp, sz, i, i, vp], i),
         "ftar_allreduce_rabenseifner_host": ([vp, vp, sz, i, i, vp], i),
         "ftar_recursive_doubling_host": ([vp, vp, sz, i, i, vp], i),
+        "ftar_allreduce_multi": ([i, pp, pp, ctypes.POINTER(sz), i, i, i, vp], i),
         "ftar_reduce_local": ([vp, vp, sz, i, i, vp], i),
         "ftar_set_reduce_variant": ([i], i),
         "ftar_comm_set_stream": ([vp, vp], i),
@@ -320,6 +324,41 @@ class Comm:
         if dtype is None:
             dtype = _dtype_of(dst)
         return lib().ftar_recursive_doubling_host(src.data_ptr(), dst.data_ptr(), count, dtype, op, self._h)
+
+    def allreduce_multi(self, tensors, out=None, op: int = SUM, algo="raben", dtype=None) -> int:
+        """One Allreduce over a list of contiguous tensors of one dtype on the comm's device: the
+        schedule `algo` ("raben" / "rd", or ALGO_*) over their dense concatenation, the result cut
+        back into `out` (None: in place).  Pair types: the packed tensors (pack_pairs) with an
+        explicit `dtype=`; the count of an entry is then its number of pairs."""
+        outs = tensors if out is None else out
+        if len(outs) != len(tensors):
+            raise FtarError("allreduce_multi: as many outputs as inputs")
+        if not 1 <= len(tensors) <= MULTI_MAX:
+            raise FtarError(f"allreduce_multi: 1 .. {MULTI_MAX} tensors")
+        algo = {"raben": ALGO_RABENSEIFNER, "rd": ALGO_RD}.get(algo, algo)
+        if algo not in (ALGO_RD, ALGO_RABENSEIFNER):
+            raise FtarError(f"allreduce_multi: unknown algo {algo!r}")
+        if len({t.dtype for t in tensors} | {t.dtype for t in outs}) != 1:
+            raise FtarError("allreduce_multi: the tensors must share one dtype")
+        for t, o in zip(tensors, outs):
+            if o.numel() != t.numel():
+                raise FtarError("allreduce_multi: an output's size differs from its input's")
+        if dtype is None:
+            dtype = _dtype_of(tensors[0])
+            counts = [t.numel() for t in tensors]
+        else:  # a pair type: only the layout pack_pairs produces, one row per pair
+            import torch
+            _pair_value_dtype(dtype)
+            want = torch.int64 if dtype == DOUBLE_INT else torch.int32
+            for t in list(tensors) + list(outs):
+                if t.dtype != want or t.dim() != 2 or t.shape[1] != 2 or not t.is_contiguous():
+                    raise FtarError(f"allreduce_multi: dtype {dtype} takes contiguous (n, 2) {want} tensors (pack_pairs)")
+            counts = [t.shape[0] for t in tensors]
+        n = len(tensors)
+        vp, sz = ctypes.c_void_p, ctypes.c_size_t
+        sb = (vp * n)(*[_ptr(t) if t.numel() else None for t in tensors])
+        rb = (vp * n)(*[_ptr(o) if o.numel() else None for o in outs])
+        return lib().ftar_allreduce_multi(algo, sb, rb, (sz * n)(*counts), n, dtype, op, self._h)
 
     def finalize(self):
         if self._h:

@@ -411,6 +411,16 @@ static void xcache_forget(ftar_comm *c, uint64_t id)
         if (c->xcache[k].id == id) c->xcache[k].id = 0;
 }
 
+/* `bytes` moved as whole elements of the widest type that divides them: int32, or a 2-byte
+ * type where a 2-byte vector has an odd count (bytes / 4 int32 elements dropped its last one) */
+static fdev_seg copy_bytes_seg(void *dst, const void *src, size_t bytes, int *dtype)
+{
+    const size_t es = bytes % 4 ? 2 : 4;
+    fdev_seg s = {FDEV_COPY, 0, dst, src, NULL, bytes / es, NULL};
+    *dtype = es == 2 ? FTAR_FLOAT16 : FTAR_INT32;
+    return s;
+}
+
 int ftar_stage_input(ftar_comm *c, const void *sbuf, size_t bytes, int alias_ok)
 {
     ftar_slot *me = &c->job.shm->slot[c->wrank];
@@ -537,8 +547,9 @@ void ftar_resolve_inputs(ftar_comm *c)
             c->export_user = 0;
             me->uid = 0; /* this call's input is the staged IN from here on (ftar_dead_input) */
             if (c->in_alias) { /* stage the whole vector: what every schedule reads from IN */
-                fdev_seg s = {FDEV_COPY, 0, c->ws[WS_IN], c->in_alias, NULL, c->in_bytes / 4, NULL};
-                ftar_run(c, FTAR_INT32, FTAR_SUM, &s, 1, FDEV_TAG_LOCAL);
+                int dt;
+                fdev_seg s = copy_bytes_seg(c->ws[WS_IN], c->in_alias, c->in_bytes, &dt);
+                ftar_run(c, dt, FTAR_SUM, &s, 1, FDEV_TAG_LOCAL);
                 ftar_drain(c);
             }
             ftar_inputs_done(c);
@@ -971,8 +982,9 @@ int ftar_single_rank(ftar_comm *c, const void *sbuf, void *rbuf, size_t bytes)
     ftar_maybe_die(c, FTAR_PH_PRE, 0, FTAR_PT_BEFORE);
     ftar_enter(c);
     if (sbuf != rbuf) {
-        fdev_seg s = {FDEV_COPY, 0, rbuf, sbuf, NULL, bytes / 4, NULL};
-        ftar_run(c, FTAR_INT32, FTAR_SUM, &s, 1, FDEV_TAG_LOCAL);
+        int dt;
+        fdev_seg s = copy_bytes_seg(rbuf, sbuf, bytes, &dt);
+        ftar_run(c, dt, FTAR_SUM, &s, 1, FDEV_TAG_LOCAL);
     }
     ftar_launched(c, FTAR_PH_PRE, 0);
     ftar_drain(c);
@@ -1149,6 +1161,118 @@ int ftar_set_profiling(ftar_comm *c, int on)
     if (!c) return FTAR_ERR_ARG;
     c->profiling = on;
     fdev_profiling(c->dev, on);
+    return FTAR_SUCCESS;
+}
+
+/* ---- one Allreduce over a list of buffers ----------------------------------- */
+
+/* The gather (scatter = 0: entries -> packed) or scatter launch: the device layer's table-driven
+ * kernel, or where it has none (host-sim) FDEV_COPY segments in groups of FDEV_MAX_SEGS. */
+static void multi_move(ftar_comm *c, void *packed, const fdev_gent *tab, int n, int dtype, int op, int scatter)
+{
+    /* nothing to return: a launch that fails ends the job in either path (ftar_launch_check, which
+     * ftar_run goes through as well, calls ftar_ctrl_abort) -- a rank never goes on to the
+     * schedule with a vector gathered in part */
+    const size_t es = ftar_esize(dtype);
+    if (fdev_gather) {
+        ftar_note_launch(c, NULL, 0);
+        ftar_launch_check(c, fdev_gather(c->dev, packed, tab, n, es, scatter, FDEV_TAG_LOCAL));
+        return;
+    }
+    for (int i = 0; i < n; i += FDEV_MAX_SEGS) {
+        fdev_seg segs[FDEV_MAX_SEGS];
+        int m = n - i < FDEV_MAX_SEGS ? n - i : FDEV_MAX_SEGS;
+        for (int k = 0; k < m; k++) {
+            void *p = (char *)packed + tab[i + k].off;
+            fdev_seg s = {FDEV_COPY, 0, scatter ? tab[i + k].ptr : p, scatter ? p : tab[i + k].ptr, NULL,
+                          tab[i + k].bytes / es, NULL};
+            segs[k] = s;
+        }
+        ftar_run(c, dtype, op, segs, m, FDEV_TAG_LOCAL);
+    }
+}
+
+/* The gather and scatter launches belong to the call's one stats record: their counters are
+ * folded into it here, since the schedule's own ftar_stats_begin resets the device layer's. */
+static void multi_fold(ftar_comm *c)
+{
+    fdev_counters k;
+    fdev_counters_get(c->dev, &k);
+    c->stats.kernel_ms += k.ms[0] + k.ms[1] + k.ms[2] + k.ms[3] + k.ms[4];
+    c->stats.kernels += k.launches[0] + k.launches[1] + k.launches[2] + k.launches[3] + k.launches[4];
+    c->stats.link_bytes += k.link_bytes;
+    c->stats.hbm_bytes += k.hbm_bytes;
+    fdev_counters_reset(c->dev);
+}
+
+static int by_ptr(const void *a, const void *b)
+{
+    const uintptr_t x = (uintptr_t)((const fdev_gent *)a)->ptr, y = (uintptr_t)((const fdev_gent *)b)->ptr;
+    return x < y ? -1 : x > y;
+}
+
+static int multi_plain(ftar_algo algo, const void *s, void *r, size_t n, ftar_dtype dtype, ftar_op op, ftar_comm *c)
+{
+    return algo == FTAR_ALGO_RD ? ftar_recursive_doubling(s, r, n, dtype, op, c)
+                                : ftar_allreduce_rabenseifner(s, r, n, dtype, op, c);
+}
+
+/* The shape of the _host entry points' unpipelined branch with a kernel as the mover: gather
+ * into hsend, the plain schedule hsend -> hrecv, scatter out of hrecv.  The schedule sees one
+ * dense vector, so block boundaries, operand order, recovery and kill points are the plain
+ * call's; every input is read (the gather is queued first on the rank's stream) before any
+ * output is written (the scatter is queued after the schedule has drained). */
+int ftar_allreduce_multi(ftar_algo algo, const void *const *sbufs, void *const *rbufs, const size_t *counts, int nbufs,
+                         ftar_dtype dtype, ftar_op op, ftar_comm *c)
+{
+    if (!c) return FTAR_ERR_ARG;
+    int rc = ftar_check_op((int)dtype, (int)op);
+    if (rc) return rc;
+    if (!sbufs || !rbufs || !counts || nbufs < 1 || nbufs > FTAR_MULTI_MAX ||
+        (algo != FTAR_ALGO_RD && algo != FTAR_ALGO_RABENSEIFNER))
+        return FTAR_ERR_ARG;
+    const size_t es = ftar_esize(dtype);
+    /* the two tables (24 KiB each at FTAR_MULTI_MAX); `in` first holds the outputs sorted by
+     * address, for the overlap check */
+    fdev_gent in[FTAR_MULTI_MAX], out[FTAR_MULTI_MAX];
+    size_t total = 0;
+    int n = 0, only = -1;
+    for (int i = 0; i < nbufs; i++) {
+        if (counts[i] == 0) continue;
+        if (counts[i] > (size_t)INT64_MAX / 16 - total || !sbufs[i] || !rbufs[i]) return FTAR_ERR_ARG;
+        const size_t b = counts[i] * es;
+        if (fdev_check_ptr(c->dev, sbufs[i], b) || fdev_check_ptr(c->dev, rbufs[i], b)) return FTAR_ERR_ARG;
+        out[n] = (fdev_gent){rbufs[i], total * es, b};
+        total += counts[i];
+        only = i;
+        n++;
+    }
+    memcpy(in, out, sizeof(fdev_gent) * (size_t)n);
+    qsort(in, (size_t)n, sizeof(fdev_gent), by_ptr);
+    for (int i = 1; i < n; i++)
+        if ((uintptr_t)in[i - 1].ptr + in[i - 1].bytes > (uintptr_t)in[i].ptr) return FTAR_ERR_ARG;
+    if (n == 0) return multi_plain(algo, NULL, NULL, 0, dtype, op, c);
+    if (n == 1) return multi_plain(algo, sbufs[only], rbufs[only], counts[only], dtype, op, c);
+    for (int i = 0, k = 0; i < nbufs; i++)
+        if (counts[i]) {
+            in[k] = (fdev_gent){(void *)(uintptr_t)sbufs[i], out[k].off, out[k].bytes};
+            k++;
+        }
+
+    ftar_ensure_staging(c, total * es);
+    ftar_stats_begin(c); /* the call's one record and call index; the schedule continues it (chunk_cont) */
+    c->stats.coalesced = n;
+    fdev_order_after(c->dev, c->user_stream); /* the inputs may still be in flight on the caller's stream */
+    multi_move(c, c->hsend, in, n, (int)dtype, (int)op, 0);
+    multi_fold(c);
+    c->chunk_cont = 1;
+    rc = multi_plain(algo, c->hsend, c->hrecv, total, dtype, op, c);
+    c->chunk_cont = 0;
+    if (rc) return rc;
+    multi_move(c, c->hrecv, out, n, (int)dtype, (int)op, 1);
+    ftar_drain(c); /* blocking: the results are in the caller's buffers */
+    multi_fold(c);
+    c->stats.wall_s = now_s() - c->t0;
     return FTAR_SUCCESS;
 }
 

@@ -96,6 +96,22 @@ int fdev_host_pinned(const void *ptr);
 
 /* Enqueue one segment kernel on the rank's stream. */
 int fdev_run(ftar_dev *d, int dtype, int op, const fdev_seg *segs, int nseg, int tag);
+/* The mover of ftar_allreduce_multi: ONE launch on the rank's stream that gathers the n (1 ..
+ * FDEV_MAX_GATHER) entries of `table` into the dense vector `packed` (scatter = 0: packed[off ..
+ * off + bytes) = ptr[0 .. bytes)), or scatters them back out of it (scatter = 1).  The entries
+ * are non-empty, ascending and dense in packed space (table[0].off = 0, table[i + 1].off =
+ * table[i].off + table[i].bytes), offsets and sizes multiples of `esize` (2, 4, 8, 16).  The
+ * table is copied: the caller's may go out of scope at once.  Weak: a device layer that does
+ * not define it (the host-sim test layer) leaves the shared host C to move the entries with
+ * fdev_run's FDEV_COPY segments. */
+typedef struct {
+    void *ptr;    /* the caller's buffer */
+    size_t off;   /* its byte offset in the packed vector */
+    size_t bytes;
+} fdev_gent;
+#define FDEV_MAX_GATHER 1024
+int fdev_gather(ftar_dev *d, void *packed, const fdev_gent *table, int n, size_t esize, int scatter, int tag)
+    __attribute__((weak));
 /* Tree reduce of nsrc (2, 4, 8 or 16) sources into out on the rank's stream:
  * out[i] = ((src0 op src1) op (src2 op src3)) op ...; bit j of remote_mask marks src[j]
  * as a peer mapping (byte accounting). */

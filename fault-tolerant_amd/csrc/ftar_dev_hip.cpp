@@ -259,6 +259,8 @@ void fdev_close(ftar_dev *d)
     if (d->sig_cnt) (void)hipFree(d->sig_cnt);
     if (d->sig_flag) (void)hipHostFree(d->sig_flag);
     if (d->gate_dw) (void)hipFree(d->gate_dw);
+    if (d->gt_dev) (void)hipFree(d->gt_dev);
+    if (d->gt_host) (void)hipHostFree(d->gt_host);
     if (d->fence_pre) (void)hipEventDestroy(d->fence_pre);
     if (d->nofence_main) (void)hipEventDestroy(d->nofence_main);
     if (d->nofence_bg) (void)hipEventDestroy(d->nofence_bg);

@@ -129,6 +129,10 @@ struct ftar_dev {
     unsigned pw_seq, pw_vval;
     int pw_pending, pw_armed;
     unsigned long long pw_launch_n;
+    // fdev_gather's table: a device buffer the kernel reads and its pinned host mirror, grown on
+    // demand (gt_cap entries per half: the gather's launch uses the first, the scatter's the second)
+    ftar::GEntry *gt_dev, *gt_host;
+    int gt_cap;
 };
 
 namespace fdevi {

@@ -307,6 +307,76 @@ int fdev_run(ftar_dev *d, int dtype, int op, const fdev_seg *segs, int nseg, int
 
 extern "C" {
 
+// The table travels through the pinned mirror by an async copy on the rank's stream, ahead of
+// the launch.  Both halves are rewritten only by a later call: ftar_allreduce_multi drains
+// before it returns, so no copy is in flight under a rewrite.
+int fdev_gather(ftar_dev *d, void *packed, const fdev_gent *table, int n, size_t esize, int scatter, int tag)
+{
+    if (!packed || !table || n < 1 || n > ftar::kMaxGather || tag < 0 || tag >= FDEV_NTAGS ||
+        !(esize == 2 || esize == 4 || esize == 8 || esize == 16)) {
+        snprintf(g_err, sizeof(g_err), "fdev_gather: bad arguments");
+        return 13;
+    }
+    size_t total = 0;
+    for (int i = 0; i < n; i++) { // dense, ascending, whole elements: what the kernel's walk relies on
+        if (!table[i].ptr || !table[i].bytes || table[i].off != total || table[i].bytes % esize) {
+            snprintf(g_err, sizeof(g_err), "fdev_gather: entry %d breaks the table's rules", i);
+            return 13;
+        }
+        total += table[i].bytes;
+    }
+    if (n > d->gt_cap) {
+        int cap = d->gt_cap ? d->gt_cap : 64;
+        while (cap < n) cap *= 2;
+        HIPCHK(hipStreamSynchronize(d->stream)); // (nothing of ours is in flight: see above)
+        if (d->gt_dev) (void)hipFree(d->gt_dev);
+        if (d->gt_host) (void)hipHostFree(d->gt_host);
+        d->gt_dev = d->gt_host = nullptr;
+        d->gt_cap = 0;
+        HIPCHK(hipMalloc((void **)&d->gt_dev, 2 * (size_t)cap * sizeof(ftar::GEntry)));
+        HIPCHK(hipHostMalloc((void **)&d->gt_host, 2 * (size_t)cap * sizeof(ftar::GEntry), hipHostMallocDefault));
+        d->gt_cap = cap;
+    }
+    ftar::GEntry *hm = d->gt_host + (scatter ? d->gt_cap : 0), *dm = d->gt_dev + (scatter ? d->gt_cap : 0);
+    for (int i = 0; i < n; i++) hm[i] = ftar::GEntry{table[i].ptr, table[i].off, table[i].bytes};
+    ftar::GatherArgs A{};
+    A.packed = (char *)packed;
+    A.tab = dm;
+    A.n = n;
+    A.es = (unsigned)esize;
+    A.total = total;
+    const size_t tiles = (total + ftar::kTileBytes - 1) / ftar::kTileBytes;
+    if (tiles > 0xffffffffull) {
+        snprintf(g_err, sizeof(g_err), "fdev_gather: vector too large");
+        return 13;
+    }
+    A.ntiles = (unsigned)tiles;
+    const unsigned grid = A.ntiles < d->max_blocks ? A.ntiles : d->max_blocks;
+    d->ctr.hbm_bytes += 2.0 * (double)total;
+    note_launch(d, d->stream, grid, true, &A.sig);
+    if (d->trace) {
+        std::vector<TrRange> user, pk;
+        for (int i = 0; i < n; i++) user.push_back({table[i].ptr, table[i].bytes});
+        pk.push_back({packed, total});
+        tr_launch(d, d->stream, &A.sig, scatter ? tr_rw(d, pk, user) : tr_rw(d, user, pk), 0, "k");
+    }
+    // (behind note_launch: a fenced marker it queued stays in front of everything of this launch)
+    HIPCHK(hipMemcpyAsync(dm, hm, (size_t)n * sizeof(ftar::GEntry), hipMemcpyHostToDevice, d->stream));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (d->profiling) {
+        e0 = get_event(d);
+        e1 = get_event(d);
+        if (e0) (void)hipEventRecord(e0, d->stream);
+    }
+    hipError_t e = ftar::launch_gather(A, scatter, grid, d->stream);
+    if (e != hipSuccess) return set_err(e, "gather_kernel launch");
+    if (d->profiling && e0 && e1) {
+        (void)hipEventRecord(e1, d->stream);
+        d->pending.push_back(Pending{e0, e1, tag});
+    }
+    return 0;
+}
+
 int fdev_run_bg(ftar_dev *d, int dtype, int op, const fdev_seg *segs, int nseg, int tag)
 {
     int rc = ensure_bg(d);

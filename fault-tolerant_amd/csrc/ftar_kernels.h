@@ -201,6 +201,87 @@ unsigned plan_tree_batch(TreeBatch *B, int p, size_t esize, unsigned max_blocks)
 unsigned cap_tree_batch(TreeBatch *B, unsigned max_total);
 hipError_t launch_tree_batch(int dtype, int op, int p, const TreeBatch &B, unsigned grid, hipStream_t s);
 
+// Table-driven gather / scatter (fdev_gather: the mover of ftar_allreduce_multi).  The table --
+// {user pointer, packed byte offset, bytes} per entry, non-empty, ascending and dense -- lives in
+// device memory (1024 entries do not fit the kernel arguments).  The grid is laid out in PACKED
+// space, one workgroup per 16 KiB tile (capped, with a stride loop), so the load is balanced
+// whatever the entries' sizes: a workgroup finds the first entry overlapping its tile by binary
+// search (gather_first) and walks the entries that follow while they overlap it (gather_piece).
+constexpr int kMaxGather = 1024;
+constexpr size_t kTileBytes = (size_t)kTileVecs * 16;
+struct GEntry {
+    void *ptr;
+    size_t off;
+    size_t bytes;
+};
+struct GatherArgs {
+    char *packed;
+    const GEntry *tab; // device memory
+    int n;
+    unsigned es;       // element size of the call: 2, 4, 8, 16
+    size_t total;      // bytes of the packed vector
+    unsigned ntiles;
+    KSignal sig;       // optional completion signal
+};
+
+// The entry holding packed byte `lo` (< total): the last one whose offset is <= lo.  (A template
+// over the pointer type: the kernel reads the table through the constant address space.)
+template <typename Tab> __host__ __device__ inline int gather_first(Tab tab, int n, size_t lo)
+{
+    int a = 0, b = n - 1;
+    while (a < b) {
+        const int m = (a + b + 1) >> 1;
+        if (tab[m].off <= lo) a = m;
+        else b = m - 1;
+    }
+    return a;
+}
+
+// What a workgroup moves for one entry inside its tile [lo, hi): `bytes` from `user` to packed
+// offset `poff` (or back).  Where the user address and the packed address are congruent mod 16
+// (vec): a head of `head` bytes up to the packed 16-byte boundary, nvec 16-byte vectors, a tail;
+// otherwise everything element by element (head = bytes, nvec = 0).  Heads, tails and unaligned
+// pieces move in units of `unit` bytes: the element size, 8 for the 16-byte type (two halves,
+// its alignment is 8), lowered to what the two addresses allow (a pair of 4-byte fields needs
+// 4-byte alignment only).  Offsets and sizes are multiples of the element size, so no element
+// straddles a piece.
+struct GPiece {
+    char *user;
+    size_t poff;
+    size_t bytes;
+    size_t head;
+    size_t nvec;
+    unsigned unit;
+    unsigned vec;
+};
+
+__host__ __device__ inline bool gather_piece(const GEntry &E, size_t lo, size_t hi, const char *packed, unsigned es,
+                                             GPiece *P)
+{
+    const size_t b = E.off > lo ? E.off : lo;
+    const size_t e = E.off + E.bytes < hi ? E.off + E.bytes : hi;
+    if (b >= e) return false;
+    P->user = (char *)E.ptr + (b - E.off);
+    P->poff = b;
+    P->bytes = e - b;
+    const uintptr_t ua = (uintptr_t)P->user, pa = (uintptr_t)packed + b;
+    unsigned unit = es < 8 ? es : 8;
+    while (unit > 1 && ((ua | pa) & (unit - 1))) unit >>= 1;
+    P->unit = unit;
+    P->vec = ((ua ^ pa) & 15) == 0;
+    if (P->vec) {
+        const size_t h = (16 - (pa & 15)) & 15;
+        P->head = h < P->bytes ? h : P->bytes;
+        P->nvec = (P->bytes - P->head) / 16;
+    } else {
+        P->head = P->bytes;
+        P->nvec = 0;
+    }
+    return true;
+}
+
+hipError_t launch_gather(const GatherArgs &A, int scatter, unsigned grid, hipStream_t s);
+
 unsigned plan_segments(const SegIn *in, int nin, size_t esize, unsigned max_blocks, KSegList *L);
 hipError_t launch_segments(int dtype, int op, const KSegList &L, unsigned grid, hipStream_t s);
 hipError_t launch_reduce_lds(int dtype, int op, void *inout, const void *in, size_t nvec, unsigned grid,

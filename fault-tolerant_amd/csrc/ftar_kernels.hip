@@ -852,6 +852,114 @@ hipError_t launch_peer_wait(const PeerWait &W, hipStream_t s)
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------
+// table-driven gather / scatter (GatherArgs, ftar_kernels.h)
+// ---------------------------------------------------------------------------------
+// User memory is streamed (read once on gather, not re-read by this rank on scatter):
+// non-temporal.  The packed side is what the schedule reads next (gather: plain stores, a small
+// call's staging copy or one-shot launch then finds them in cache) or has just written
+// (scatter: plain loads).
+// Both sides are global memory (device or mapped pinned host memory), which the compiler cannot
+// see for pointers loaded from the table: said here, so that it emits global_* and not flat_*.
+#define FTAR_GLOBAL __attribute__((address_space(1)))
+template <bool SCATTER, typename U>
+__device__ __forceinline__ void move_units(char *user, char *packed, size_t bytes, unsigned tid, unsigned nth)
+{
+    FTAR_GLOBAL U *u = (FTAR_GLOBAL U *)user, *k = (FTAR_GLOBAL U *)packed;
+    const size_t n = bytes / sizeof(U);
+    for (size_t i = tid; i < n; i += nth) {
+        if (SCATTER) __builtin_nontemporal_store(k[i], u + i);
+        else k[i] = __builtin_nontemporal_load(u + i);
+    }
+}
+
+template <bool SCATTER>
+__device__ __forceinline__ void move_small(char *user, char *packed, size_t bytes, unsigned unit, unsigned tid,
+                                           unsigned nth)
+{
+    if (bytes == 0) return;
+    if (unit == 8) move_units<SCATTER, unsigned long long>(user, packed, bytes, tid, nth);
+    else if (unit == 4) move_units<SCATTER, unsigned>(user, packed, bytes, tid, nth);
+    else if (unit == 2) move_units<SCATTER, unsigned short>(user, packed, bytes, tid, nth);
+    else move_units<SCATTER, unsigned char>(user, packed, bytes, tid, nth);
+}
+
+// One piece by `nth` threads (the workgroup, or one wave for a small piece), this one `tid`.
+template <bool SCATTER>
+__device__ __forceinline__ void move_piece(const GPiece &P, char *packed, unsigned tid, unsigned nth)
+{
+    char *k = packed + P.poff;
+    move_small<SCATTER>(P.user, k, P.head, P.unit, tid, nth);
+    if (!P.vec) return;
+    FTAR_GLOBAL v4u *U = (FTAR_GLOBAL v4u *)(P.user + P.head), *K = (FTAR_GLOBAL v4u *)(k + P.head);
+    size_t i = tid;
+    // kUnroll independent 16-byte loads in flight per lane, as the segment kernel's tiles
+    for (; i + (size_t)(kUnroll - 1) * nth < P.nvec; i += (size_t)kUnroll * nth) {
+        v4u v[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; u++)
+            v[u] = SCATTER ? K[i + (size_t)u * nth] : __builtin_nontemporal_load(U + i + (size_t)u * nth);
+#pragma unroll
+        for (int u = 0; u < kUnroll; u++) {
+            if (SCATTER) __builtin_nontemporal_store(v[u], U + i + (size_t)u * nth);
+            else K[i + (size_t)u * nth] = v[u];
+        }
+    }
+    for (; i < P.nvec; i += nth) {
+        if (SCATTER) __builtin_nontemporal_store(K[i], U + i);
+        else K[i] = __builtin_nontemporal_load(U + i);
+    }
+    const size_t done = P.head + P.nvec * 16;
+    move_small<SCATTER>(P.user + done, k + done, P.bytes - done, P.unit, tid, nth);
+}
+
+constexpr size_t kWavePiece = 1024; // a piece below this many bytes is one wave's; the waves take entries in turn
+
+template <bool SCATTER>
+__global__ __launch_bounds__(kBlock) void gather_kernel(GatherArgs A)
+{
+    signal_acquire(A.sig);
+    // blockIdx and the wave's number are wave-uniform: readfirstlane keeps the tile bounds, the
+    // binary search and the table reads in SGPRs (scalar loads of the table)
+    const unsigned b0 = (unsigned)__builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    const unsigned nb = (unsigned)__builtin_amdgcn_readfirstlane((int)gridDim.x);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned lane = threadIdx.x & 63;
+    // The table is not written while the kernel runs (the copy that filled it is in front of the
+    // launch on the stream): read through the constant address space, its uniform loads are
+    // scalar loads out of the scalar cache -- the search and the walk are a chain of dependent
+    // loads in front of every tile, and as vector loads they cost an L2 round trip each.
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) GEntry *CTab;
+#else // (the host pass only parses the kernel)
+    typedef const GEntry *CTab;
+#endif
+    const CTab tab = (CTab)A.tab;
+    for (unsigned t = b0; t < A.ntiles; t += nb) {
+        const size_t lo = (size_t)t * kTileBytes;
+        const size_t hi = lo + kTileBytes < A.total ? lo + kTileBytes : A.total;
+        for (int e = __builtin_amdgcn_readfirstlane(gather_first(tab, A.n, lo)); e < A.n; e++) {
+            const GEntry E = {tab[e].ptr, tab[e].off, tab[e].bytes};
+            GPiece P;
+            if (!gather_piece(E, lo, hi, A.packed, A.es, &P)) break; // entries ascend: past the tile
+            if (P.bytes >= kWavePiece) move_piece<SCATTER>(P, A.packed, threadIdx.x, kBlock);
+            else if ((e & 3) == wave) move_piece<SCATTER>(P, A.packed, lane, 64);
+            if (E.off + E.bytes >= hi) break; // the tile ends inside this entry: no look at the next
+        }
+    }
+    signal_done(A.sig);
+}
+
+hipError_t launch_gather(const GatherArgs &A, int scatter, unsigned grid, hipStream_t s)
+{
+    if (!A.packed || !A.tab || A.n < 1 || A.n > kMaxGather || grid == 0 || grid > A.ntiles ||
+        (size_t)A.ntiles != (A.total + kTileBytes - 1) / kTileBytes)
+        return hipErrorInvalidValue;
+    if (scatter) hipLaunchKernelGGL(gather_kernel<true>, dim3(grid), dim3(kBlock), 0, s, A);
+    else hipLaunchKernelGGL(gather_kernel<false>, dim3(grid), dim3(kBlock), 0, s, A);
+    return hipGetLastError();
+}
+
 hipError_t launch_segments(int dtype, int op, const KSegList &L, unsigned grid, hipStream_t s)
 {
     switch (dtype) {

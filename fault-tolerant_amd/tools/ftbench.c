@@ -15,6 +15,10 @@
  * ranks from 4 ranks on -- and its rank as the index; the check recomputes each element's winner
  * (the largest value, the lowest rank among equals) on the host.
  *
+ * FTBENCH_MULTI=K (float32 only, 1 <= K <= min(count, FTAR_MULTI_MAX)): the job's `count` is split into
+ * K buffers as equal as possible, each send and receive buffer a hipMalloc of its own, and every
+ * call is one ftar_allreduce_multi over the list; the check and the output line are unchanged.
+ *
  * Every rank hipMallocs float32 send / receive vectors of `count` elements on its device,
  * fills the send vector with its original rank (the reference drivers' input,
  * rd/recursive_doubling.c:112-115 / raben/rabenseifner.c:408-411, as float32: every
@@ -112,6 +116,12 @@ int main(int argc, char **argv)
     ftar_world_size(comm, &wsize);
     ftar_comm_device(comm, &dev);
     CHECK_HIP(hipSetDevice(dev));
+    const char *me = getenv("FTBENCH_MULTI");
+    const int multi = me && *me ? atoi(me) : 0;
+    if (me && *me && (multi < 1 || multi > FTAR_MULTI_MAX || (size_t)multi > count || dt16 || dtpair)) {
+        fprintf(stderr, "ftbench: FTBENCH_MULTI=%s: 1 .. min(count, %d) buffers of float32\n", me, FTAR_MULTI_MAX);
+        return 2;
+    }
     if (dt16) return run16(rd, count, calls, (ftar_dtype)dt16, comm, wrank, wsize, dev);
     if (dtpair) return runpair(rd, count, calls, (ftar_dtype)dtpair, comm, wrank, wsize, dev);
 
@@ -125,16 +135,36 @@ int main(int argc, char **argv)
     if (!h) return 4;
     for (size_t i = 0; i < count; i++) h[i] = pattern ? (float)((7 * i + 13 * (size_t)wrank) % 4096) : (float)wrank;
     float *s = NULL, *r = NULL;
-    CHECK_HIP(hipMalloc((void **)&s, count * sizeof(float)));
-    CHECK_HIP(hipMalloc((void **)&r, count * sizeof(float)));
-    CHECK_HIP(hipMemcpy(s, h, count * sizeof(float), hipMemcpyHostToDevice));
+    static const void *ms_[FTAR_MULTI_MAX];
+    static void *mr_[FTAR_MULTI_MAX];
+    static size_t mc_[FTAR_MULTI_MAX];
+    if (multi) {
+        size_t off = 0;
+        for (int k = 0; k < multi; k++) {
+            mc_[k] = count / (size_t)multi + ((size_t)k < count % (size_t)multi);
+            void *a = NULL;
+            CHECK_HIP(hipMalloc(&a, mc_[k] * sizeof(float)));
+            CHECK_HIP(hipMalloc(&mr_[k], mc_[k] * sizeof(float)));
+            CHECK_HIP(hipMemcpy(a, h + off, mc_[k] * sizeof(float), hipMemcpyHostToDevice));
+            ms_[k] = a;
+            off += mc_[k];
+        }
+    } else {
+        CHECK_HIP(hipMalloc((void **)&s, count * sizeof(float)));
+        CHECK_HIP(hipMalloc((void **)&r, count * sizeof(float)));
+        CHECK_HIP(hipMemcpy(s, h, count * sizeof(float), hipMemcpyHostToDevice));
+    }
     CHECK_HIP(hipDeviceSynchronize());
 
     double ms[MAX_CALLS], value[MAX_CALLS], hbm[MAX_CALLS];
     int rc[MAX_CALLS], rec[MAX_CALLS], size_after[MAX_CALLS], uniform[MAX_CALLS], step0_copy = 0;
     for (int c = 0; c < calls; c++) {
-        rc[c] = rd ? ftar_recursive_doubling(s, r, count, FTAR_FLOAT32, FTAR_SUM, comm)
-                   : ftar_allreduce_rabenseifner(s, r, count, FTAR_FLOAT32, FTAR_SUM, comm);
+        if (multi)
+            rc[c] = ftar_allreduce_multi(rd ? FTAR_ALGO_RD : FTAR_ALGO_RABENSEIFNER, ms_, mr_, mc_, multi, FTAR_FLOAT32,
+                                         FTAR_SUM, comm);
+        else
+            rc[c] = rd ? ftar_recursive_doubling(s, r, count, FTAR_FLOAT32, FTAR_SUM, comm)
+                       : ftar_allreduce_rabenseifner(s, r, count, FTAR_FLOAT32, FTAR_SUM, comm);
         ftar_stats st;
         ftar_last_stats(comm, &st);
         ms[c] = st.wall_s * 1e3;
@@ -143,7 +173,13 @@ int main(int argc, char **argv)
         size_after[c] = st.comm_size_after;
         step0_copy |= st.step0_copy;
         /* outside the call's timed region: read the result back and check it is uniform */
-        CHECK_HIP(hipMemcpy(h, r, count * sizeof(float), hipMemcpyDeviceToHost));
+        if (multi) {
+            size_t off = 0;
+            for (int k = 0; k < multi; off += mc_[k], k++)
+                CHECK_HIP(hipMemcpy(h + off, mr_[k], mc_[k] * sizeof(float), hipMemcpyDeviceToHost));
+        } else {
+            CHECK_HIP(hipMemcpy(h, r, count * sizeof(float), hipMemcpyDeviceToHost));
+        }
         value[c] = h[0];
         uniform[c] = 1;
         const int members = size_after[c]; /* the original ranks 0 .. members-1 (no fault) */
@@ -169,6 +205,10 @@ int main(int argc, char **argv)
     printf("]}\n");
     fflush(stdout);
     ftar_finalize(comm);
+    for (int k = 0; k < multi; k++) {
+        (void)hipFree((void *)(uintptr_t)ms_[k]);
+        (void)hipFree(mr_[k]);
+    }
     (void)hipFree(s);
     (void)hipFree(r);
     free(h);

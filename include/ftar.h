@@ -202,6 +202,33 @@ int ftar_allreduce_rabenseifner_host(const void *sbuf, void *rbuf, size_t count,
 int ftar_recursive_doubling_host(const void *src, void *dst, size_t count,
                                  ftar_dtype dtype, ftar_op op, ftar_comm *comm);
 
+/* One Allreduce over a LIST of device buffers (a training job's gradient tensors): exactly the
+ * Allreduce named by `algo` over the dense concatenation sbufs[0] ++ sbufs[1] ++ ... -- entries
+ * in list order, in elements, no padding between them -- with the result cut back into rbufs[i]
+ * at the same offsets.  "Exactly" includes the bits (a caller who copied the tensors into one
+ * vector and called the plain entry point gets the same answer bit for bit), the recovery and
+ * abort outcomes, the comm re-targeting, the FTAR_KILL call index (one call) and the return code.
+ * The library gathers the entries into a staging vector of its own with one kernel launch, runs
+ * the plain schedule on it and scatters the result with a second launch: one fixed cost instead
+ * of nbufs, and the peers see one stable library-owned send buffer whatever the caller's are.
+ *   - collective: every live rank passes the same counts;
+ *   - sbufs[i] == rbufs[i] (in place) is allowed per entry; output ranges of different entries
+ *     must be pairwise disjoint; an output may overlap another entry's input (every input is read
+ *     before any output is written);
+ *   - entries with counts[i] == 0 are skipped, their pointers not looked at;
+ *   - exactly one non-empty entry goes straight to the plain entry point (no copies); a total of
+ *     0 elements returns what the plain call with count == 0 returns.
+ * FTAR_ERR_ARG, before anything is launched or any barrier entered: comm, sbufs, rbufs or counts
+ * NULL, nbufs < 1 or > FTAR_MULTI_MAX, an unknown algo, two overlapping outputs, a non-empty
+ * buffer the device entry points would refuse (above).  The op / dtype check comes first and
+ * keeps its codes.  If the schedule returns an error no rbufs[i] is written.
+ * Costs 2 x the largest total so far in device memory (the staging of the _host entry points). */
+typedef enum { FTAR_ALGO_RD = 0, FTAR_ALGO_RABENSEIFNER = 1 } ftar_algo;
+#define FTAR_MULTI_MAX 1024
+int ftar_allreduce_multi(ftar_algo algo, const void *const *sbufs, void *const *rbufs,
+                         const size_t *counts, int nbufs,
+                         ftar_dtype dtype, ftar_op op, ftar_comm *comm);
+
 /* MPI_Reduce_local(in, inout, count, dtype, op) on the device:
  * inout[i] = in[i] (op) inout[i] with the reference's operand roles.
  * `stream` is a hipStream_t (NULL = null stream); the call is asynchronous.
@@ -306,6 +333,7 @@ typedef struct {
                                 cumulative since ftar_init */
     int    peer_waits;       /* mesh allgathers ordered behind the peers' trees on the device (FTAR_OPT_MESH_WAIT) */
     int    peer_wait_skips;  /* ... of them given up (a peer died, or the wait timed out) and settled by an agree */
+    int    coalesced;        /* buffers ftar_allreduce_multi gathered for this call (0: a plain or straight-through call) */
 } ftar_stats;
 
 int ftar_last_stats(const ftar_comm *comm, ftar_stats *out);
