@@ -117,6 +117,7 @@ def lib():
         "ftar_allreduce_rabenseifner_host": ([vp, vp, sz, i, i, vp], i),
         "ftar_recursive_doubling_host": ([vp, vp, sz, i, i, vp], i),
         "ftar_allreduce_multi": ([i, pp, pp, ctypes.POINTER(sz), i, i, i, vp], i),
+        "ftar_allreduce_multi_acc32": ([i, pp, pp, ctypes.POINTER(sz), i, i, i, ctypes.c_float, vp], i),
         "ftar_reduce_local": ([vp, vp, sz, i, i, vp], i),
         "ftar_set_reduce_variant": ([i], i),
         "ftar_comm_set_stream": ([vp, vp], i),
@@ -359,6 +360,35 @@ class Comm:
         sb = (vp * n)(*[_ptr(t) if t.numel() else None for t in tensors])
         rb = (vp * n)(*[_ptr(o) if o.numel() else None for o in outs])
         return lib().ftar_allreduce_multi(algo, sb, rb, (sz * n)(*counts), n, dtype, op, self._h)
+
+    def allreduce_multi_acc32(self, tensors, out=None, op: int = SUM, algo="raben", scale: float = 1.0) -> int:
+        """allreduce_multi for lists of contiguous torch.float16 or torch.bfloat16 tensors with
+        float32 accumulation: every element is widened to float32 (exact), the float32 schedule
+        `algo` runs on the dense concatenation, and out[i] (None: in place) receives
+        scale * result rounded once to nearest even.  The scale is the caller's (1 / ranks for a
+        mean); it is applied whatever the op."""
+        import torch
+        outs = tensors if out is None else out
+        if len(outs) != len(tensors):
+            raise FtarError("allreduce_multi_acc32: as many outputs as inputs")
+        if not 1 <= len(tensors) <= MULTI_MAX:
+            raise FtarError(f"allreduce_multi_acc32: 1 .. {MULTI_MAX} tensors")
+        algo = {"raben": ALGO_RABENSEIFNER, "rd": ALGO_RD}.get(algo, algo)
+        if algo not in (ALGO_RD, ALGO_RABENSEIFNER):
+            raise FtarError(f"allreduce_multi_acc32: unknown algo {algo!r}")
+        if len({t.dtype for t in tensors} | {t.dtype for t in outs}) != 1:
+            raise FtarError("allreduce_multi_acc32: the tensors must share one dtype")
+        if tensors[0].dtype not in (torch.float16, torch.bfloat16):
+            raise FtarError("allreduce_multi_acc32: float16 or bfloat16 tensors (float32 lists: allreduce_multi)")
+        for t, o in zip(tensors, outs):
+            if o.numel() != t.numel():
+                raise FtarError("allreduce_multi_acc32: an output's size differs from its input's")
+        n = len(tensors)
+        vp, sz = ctypes.c_void_p, ctypes.c_size_t
+        sb = (vp * n)(*[_ptr(t) if t.numel() else None for t in tensors])
+        rb = (vp * n)(*[_ptr(o) if o.numel() else None for o in outs])
+        return lib().ftar_allreduce_multi_acc32(algo, sb, rb, (sz * n)(*[t.numel() for t in tensors]), n,
+                                                _dtype_of(tensors[0]), op, float(scale), self._h)
 
     def finalize(self):
         if self._h:

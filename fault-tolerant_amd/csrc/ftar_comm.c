@@ -1276,6 +1276,63 @@ int ftar_allreduce_multi(ftar_algo algo, const void *const *sbufs, void *const *
     return FTAR_SUCCESS;
 }
 
+/* The same shape with float32 staging for lists of 2-byte floats: the gather widens into hsend,
+ * the plain FLOAT32 schedule runs hsend -> hrecv, the scatter stores scale * hrecv[j] rounded
+ * once.  The tables count packed bytes (4 per element, fdev_gather_cvt); the checks are
+ * ftar_allreduce_multi's on the user ranges (2 per element).  No straight-through case: one
+ * entry is converted like any other. */
+int ftar_allreduce_multi_acc32(ftar_algo algo, const void *const *sbufs, void *const *rbufs, const size_t *counts,
+                               int nbufs, ftar_dtype dtype, ftar_op op, float scale, ftar_comm *c)
+{
+    if (!c) return FTAR_ERR_ARG;
+    int rc = ftar_check_op((int)dtype, (int)op);
+    if (rc) return rc;
+    if ((dtype != FTAR_FLOAT16 && dtype != FTAR_BFLOAT16) || !fdev_gather_cvt || !isfinite(scale) || !sbufs || !rbufs ||
+        !counts || nbufs < 1 || nbufs > FTAR_MULTI_MAX || (algo != FTAR_ALGO_RD && algo != FTAR_ALGO_RABENSEIFNER))
+        return FTAR_ERR_ARG;
+    fdev_gent in[FTAR_MULTI_MAX], out[FTAR_MULTI_MAX];
+    size_t total = 0;
+    int n = 0;
+    for (int i = 0; i < nbufs; i++) {
+        if (counts[i] == 0) continue;
+        if (counts[i] > (size_t)INT64_MAX / 16 - total || !sbufs[i] || !rbufs[i]) return FTAR_ERR_ARG;
+        if (((uintptr_t)sbufs[i] | (uintptr_t)rbufs[i]) & 1) return FTAR_ERR_ARG;
+        if (fdev_check_ptr(c->dev, sbufs[i], counts[i] * 2) || fdev_check_ptr(c->dev, rbufs[i], counts[i] * 2))
+            return FTAR_ERR_ARG;
+        out[n] = (fdev_gent){rbufs[i], total * 4, counts[i] * 4};
+        total += counts[i];
+        n++;
+    }
+    memcpy(in, out, sizeof(fdev_gent) * (size_t)n); /* the outputs sorted by address, for the overlap check */
+    qsort(in, (size_t)n, sizeof(fdev_gent), by_ptr);
+    for (int i = 1; i < n; i++)
+        if ((uintptr_t)in[i - 1].ptr + in[i - 1].bytes / 2 > (uintptr_t)in[i].ptr) return FTAR_ERR_ARG;
+    if (n == 0) return multi_plain(algo, NULL, NULL, 0, FTAR_FLOAT32, op, c);
+    for (int i = 0, k = 0; i < nbufs; i++)
+        if (counts[i]) {
+            in[k] = (fdev_gent){(void *)(uintptr_t)sbufs[i], out[k].off, out[k].bytes};
+            k++;
+        }
+
+    ftar_ensure_staging(c, total * 4);
+    ftar_stats_begin(c);
+    c->stats.coalesced = n;
+    fdev_order_after(c->dev, c->user_stream);
+    ftar_note_launch(c, NULL, 0);
+    ftar_launch_check(c, fdev_gather_cvt(c->dev, c->hsend, in, n, (int)dtype, 1.0f, 0, FDEV_TAG_LOCAL));
+    multi_fold(c);
+    c->chunk_cont = 1;
+    rc = multi_plain(algo, c->hsend, c->hrecv, total, FTAR_FLOAT32, op, c);
+    c->chunk_cont = 0;
+    if (rc) return rc;
+    ftar_note_launch(c, NULL, 0);
+    ftar_launch_check(c, fdev_gather_cvt(c->dev, c->hrecv, out, n, (int)dtype, scale, 1, FDEV_TAG_LOCAL));
+    ftar_drain(c); /* blocking: the results are in the caller's buffers */
+    multi_fold(c);
+    c->stats.wall_s = now_s() - c->t0;
+    return FTAR_SUCCESS;
+}
+
 /* ---- local reduce --------------------------------------------------------- */
 
 int ftar_reduce_local(const void *in, void *inout, size_t count, ftar_dtype dtype, ftar_op op, void *stream)

@@ -112,6 +112,14 @@ typedef struct {
 #define FDEV_MAX_GATHER 1024
 int fdev_gather(ftar_dev *d, void *packed, const fdev_gent *table, int n, size_t esize, int scatter, int tag)
     __attribute__((weak));
+/* The converting mover of ftar_allreduce_multi_acc32: the same launch between user buffers of
+ * the 2-byte float type `dtype` (16, 17) and a packed float32 vector.  `off` and `bytes` of the
+ * table count PACKED bytes (4 per element; entry i's user buffer holds bytes / 4 elements of 2
+ * bytes, 2-byte aligned).  scatter = 0 widens exactly; scatter = 1 stores scale * packed[j],
+ * rounded once to nearest even.  Weak as well; without it the 2-byte types do not exist either
+ * (fdev_has_dtype), so the shared host C has nothing to fall back to and refuses the call. */
+int fdev_gather_cvt(ftar_dev *d, void *packed, const fdev_gent *table, int n, int dtype, float scale, int scatter,
+                    int tag) __attribute__((weak));
 /* Tree reduce of nsrc (2, 4, 8 or 16) sources into out on the rank's stream:
  * out[i] = ((src0 op src1) op (src2 op src3)) op ...; bit j of remote_mask marks src[j]
  * as a peer mapping (byte accounting). */

@@ -310,7 +310,10 @@ extern "C" {
 // The table travels through the pinned mirror by an async copy on the rank's stream, ahead of
 // the launch.  Both halves are rewritten only by a later call: ftar_allreduce_multi drains
 // before it returns, so no copy is in flight under a rewrite.
-int fdev_gather(ftar_dev *d, void *packed, const fdev_gent *table, int n, size_t esize, int scatter, int tag)
+// `cvt` = 0: the plain mover.  Otherwise the 2-byte float type of the user buffers of the
+// converting mover: esize = 4, the table in packed bytes, the user side half as many.
+static int gather_launch(ftar_dev *d, void *packed, const fdev_gent *table, int n, size_t esize, int cvt, float scale,
+                         int scatter, int tag)
 {
     if (!packed || !table || n < 1 || n > ftar::kMaxGather || tag < 0 || tag >= FDEV_NTAGS ||
         !(esize == 2 || esize == 4 || esize == 8 || esize == 16)) {
@@ -352,11 +355,11 @@ int fdev_gather(ftar_dev *d, void *packed, const fdev_gent *table, int n, size_t
     }
     A.ntiles = (unsigned)tiles;
     const unsigned grid = A.ntiles < d->max_blocks ? A.ntiles : d->max_blocks;
-    d->ctr.hbm_bytes += 2.0 * (double)total;
+    d->ctr.hbm_bytes += (cvt ? 1.5 : 2.0) * (double)total; // (converting: 2 + 4 bytes per element)
     note_launch(d, d->stream, grid, true, &A.sig);
     if (d->trace) {
         std::vector<TrRange> user, pk;
-        for (int i = 0; i < n; i++) user.push_back({table[i].ptr, table[i].bytes});
+        for (int i = 0; i < n; i++) user.push_back({table[i].ptr, cvt ? table[i].bytes / 2 : table[i].bytes});
         pk.push_back({packed, total});
         tr_launch(d, d->stream, &A.sig, scatter ? tr_rw(d, pk, user) : tr_rw(d, user, pk), 0, "k");
     }
@@ -368,13 +371,34 @@ int fdev_gather(ftar_dev *d, void *packed, const fdev_gent *table, int n, size_t
         e1 = get_event(d);
         if (e0) (void)hipEventRecord(e0, d->stream);
     }
-    hipError_t e = ftar::launch_gather(A, scatter, grid, d->stream);
-    if (e != hipSuccess) return set_err(e, "gather_kernel launch");
+    hipError_t e = cvt ? ftar::launch_gather_cvt(A, cvt, scale, scatter, grid, d->stream)
+                       : ftar::launch_gather(A, scatter, grid, d->stream);
+    if (e != hipSuccess) return set_err(e, cvt ? "gather_cvt_kernel launch" : "gather_kernel launch");
     if (d->profiling && e0 && e1) {
         (void)hipEventRecord(e1, d->stream);
         d->pending.push_back(Pending{e0, e1, tag});
     }
     return 0;
+}
+
+int fdev_gather(ftar_dev *d, void *packed, const fdev_gent *table, int n, size_t esize, int scatter, int tag)
+{
+    return gather_launch(d, packed, table, n, esize, 0, 1.0f, scatter, tag);
+}
+
+int fdev_gather_cvt(ftar_dev *d, void *packed, const fdev_gent *table, int n, int dtype, float scale, int scatter,
+                    int tag)
+{
+    if (dtype != ftar::kFloat16 && dtype != ftar::kBFloat16) {
+        snprintf(g_err, sizeof(g_err), "fdev_gather_cvt: not a 2-byte float type");
+        return 13;
+    }
+    for (int i = 0; table && i < n; i++)
+        if ((uintptr_t)table[i].ptr & 1) {
+            snprintf(g_err, sizeof(g_err), "fdev_gather_cvt: entry %d is not 2-byte aligned", i);
+            return 13;
+        }
+    return gather_launch(d, packed, table, n, 4, dtype, scale, scatter, tag);
 }
 
 int fdev_run_bg(ftar_dev *d, int dtype, int op, const fdev_seg *segs, int nseg, int tag)

@@ -282,6 +282,59 @@ __host__ __device__ inline bool gather_piece(const GEntry &E, size_t lo, size_t 
 
 hipError_t launch_gather(const GatherArgs &A, int scatter, unsigned grid, hipStream_t s);
 
+// The converting sibling (fdev_gather_cvt: the mover of ftar_allreduce_multi_acc32).  The user
+// buffers hold 2-byte floats, the packed vector float32: the same table, grid and walk, with
+// `off` and `bytes` of an entry counted in PACKED bytes (4 per element), so a tile is 4096
+// elements = 8 KiB of user memory, and GatherArgs::es = 4.  Element j of a piece sits at
+// user + 2 j and packed + 4 j: the two sides advance at different rates, so "co-aligned" is a
+// property of an element, not of the two addresses.  Class k (8, 4, 2 elements per access: 16 /
+// 32, 8 / 16, 4 / 8 bytes of user / packed memory) fits a piece when the first element whose
+// user address is a multiple of 2 k has a packed address that is a multiple of 4 k; the widest
+// class that fits is taken -- the widest one, one 16-byte user access against two 16-byte packed
+// ones, exactly where the element at which the user address reaches a 16-byte boundary has its
+// packed address on a 32-byte boundary.  `head` elements in front of that element and the
+// tail behind the last whole group go element by element (2 / 4 bytes, always aligned: user
+// pointers are 2-byte aligned, packed offsets multiples of 4); k = 1: the whole piece does
+// (head = n, nvec = 0).  Pieces begin and end on elements: nothing straddles.
+struct CPiece {
+    char *user;   // first element's user address
+    size_t poff;  // its packed byte offset
+    size_t n;     // elements
+    size_t head;  // elements before the first group
+    size_t nvec;  // groups of k elements
+    unsigned k;   // 8, 4, 2 or 1
+};
+
+__host__ __device__ inline bool cvt_piece(const GEntry &E, size_t lo, size_t hi, const char *packed, CPiece *P)
+{
+    const size_t b = E.off > lo ? E.off : lo;
+    const size_t e = E.off + E.bytes < hi ? E.off + E.bytes : hi;
+    if (b >= e) return false;
+    P->user = (char *)E.ptr + (b - E.off) / 2;
+    P->poff = b;
+    P->n = (e - b) / 4;
+    const uintptr_t ua = (uintptr_t)P->user, pa = (uintptr_t)packed + b;
+    unsigned k = 8;
+    size_t h = 0;
+    for (; k > 1; k >>= 1) {
+        h = (size_t)(((uintptr_t)0 - ua) & (2 * k - 1)) / 2; // elements up to the user boundary of 2 k bytes
+        if (((pa + 4 * h) & (4 * k - 1)) == 0) break;
+    }
+    P->k = k;
+    if (k == 1) {
+        P->head = P->n;
+        P->nvec = 0;
+    } else {
+        P->head = h < P->n ? h : P->n;
+        P->nvec = (P->n - P->head) / k;
+    }
+    return true;
+}
+
+// dtype: kFloat16 or kBFloat16.  scale: applied on scatter only (packed float32 -> scale * a,
+// rounded once to nearest even into the 2-byte type); the gather widens exactly.
+hipError_t launch_gather_cvt(const GatherArgs &A, int dtype, float scale, int scatter, unsigned grid, hipStream_t s);
+
 unsigned plan_segments(const SegIn *in, int nin, size_t esize, unsigned max_blocks, KSegList *L);
 hipError_t launch_segments(int dtype, int op, const KSegList &L, unsigned grid, hipStream_t s);
 hipError_t launch_reduce_lds(int dtype, int op, void *inout, const void *in, size_t nvec, unsigned grid,

@@ -960,6 +960,179 @@ hipError_t launch_gather(const GatherArgs &A, int scatter, unsigned grid, hipStr
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------
+// converting gather / scatter (CPiece, ftar_kernels.h): 2-byte floats <-> packed float32
+// ---------------------------------------------------------------------------------
+// Widening is exact (bfloat16: the float's upper half; float16: v_cvt_f32_f16 with the f16
+// denormal mode on, so subnormals convert, not flush).  Narrowing is ONE rounding to nearest
+// even of scale * a, the product one float32 multiplication (subnormals kept: the f32 denormal
+// mode is on as well; -ffp-contract=off, and there is nothing beside it to fuse with):
+// v_cvt_pk_bf16_f32 as in apply_bf16, v_cvt_f16_f32 / v_cvt_pk_f16_f32 under the default
+// rounding mode -- never the cvt_pkrtz builtin, which truncates.
+template <typename T> __device__ __forceinline__ float widen16(uint16_t b);
+template <> __device__ __forceinline__ float widen16<bf16_t>(uint16_t b) { return bf16_widen(bf16_t{b}); }
+template <> __device__ __forceinline__ float widen16<f16_t>(uint16_t b) { return (float)__builtin_bit_cast(_Float16, b); }
+// The compiler's own selection for float16 forced one thing: it folds (_Float16)(scale * a) into
+// v_fma_mixlo_f16 scale, a, 0 -- an addend of +0 turns a product of -0 into +0, and the
+// multiplication is no longer an instruction of its own.  An empty asm statement between the two
+// makes the product opaque (it emits nothing), so the multiplication stays v_mul_f32 /
+// v_pk_mul_f32 and the conversion v_cvt_f16_f32 / v_cvt_pk_f16_f32.
+#define FTAR_OPAQUE_VGPR(x) __asm__("" : "+v"(x))
+template <typename T> __device__ __forceinline__ uint16_t narrow1(float a, float scale);
+template <> __device__ __forceinline__ uint16_t narrow1<bf16_t>(float a, float scale)
+{
+    return __builtin_bit_cast(uint16_t, (__bf16)(scale * a));
+}
+template <> __device__ __forceinline__ uint16_t narrow1<f16_t>(float a, float scale)
+{
+    float r = scale * a;
+    FTAR_OPAQUE_VGPR(r);
+    return __builtin_bit_cast(uint16_t, (_Float16)r);
+}
+template <typename T> __device__ __forceinline__ uint32_t narrow2(f2_t a, float scale);
+template <> __device__ __forceinline__ uint32_t narrow2<bf16_t>(f2_t a, float scale)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(a * scale, b2_t));
+}
+template <> __device__ __forceinline__ uint32_t narrow2<f16_t>(f2_t a, float scale)
+{
+    f2_t r = a * scale;
+    FTAR_OPAQUE_VGPR(r);
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(r, h2_t));
+}
+
+// One access of class K: K elements, 2 K bytes of user memory against 4 K bytes of packed memory
+// (K = 8: global_load/store_dwordx4 on the user side, two of them on the packed side).
+typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float v8f __attribute__((ext_vector_type(8)));
+template <int K> struct CvtAccess;
+template <> struct CvtAccess<8> { typedef v4u U; typedef v8f P; };
+template <> struct CvtAccess<4> { typedef v2u U; typedef v4f P; };
+template <> struct CvtAccess<2> { typedef unsigned int U; typedef v2f P; };
+template <> struct CvtAccess<1> { typedef unsigned short U; typedef float P; };
+
+template <typename T, int K>
+__device__ __forceinline__ typename CvtAccess<K>::P widen_group(typename CvtAccess<K>::U u)
+{
+    uint16_t h[K];
+    float f[K];
+    __builtin_memcpy(h, &u, 2 * K);
+#pragma unroll
+    for (int j = 0; j < K; j++) f[j] = widen16<T>(h[j]);
+    typename CvtAccess<K>::P p;
+    __builtin_memcpy(&p, f, 4 * K);
+    return p;
+}
+
+template <typename T, int K>
+__device__ __forceinline__ typename CvtAccess<K>::U narrow_group(typename CvtAccess<K>::P p, float scale)
+{
+    typename CvtAccess<K>::U u;
+    if constexpr (K == 1) {
+        u = narrow1<T>(p, scale);
+    } else { // two elements per 32-bit register: one packed multiplication, one packed conversion
+        f2_t f[K / 2];
+        uint32_t h[K / 2];
+        __builtin_memcpy(f, &p, 4 * K);
+#pragma unroll
+        for (int j = 0; j < K / 2; j++) h[j] = narrow2<T>(f[j], scale);
+        __builtin_memcpy(&u, h, 2 * K);
+    }
+    return u;
+}
+
+// `ng` groups of K elements by `nth` threads; user memory non-temporal, packed memory plain (as
+// move_units above); kUnroll independent loads in flight per lane, as move_piece
+template <typename T, bool SCATTER, int K>
+__device__ __forceinline__ void cvt_groups(char *user, char *packed, size_t ng, float scale, unsigned tid, unsigned nth)
+{
+    typedef typename CvtAccess<K>::U UV;
+    typedef typename CvtAccess<K>::P PV;
+    FTAR_GLOBAL UV *U = (FTAR_GLOBAL UV *)user;
+    FTAR_GLOBAL PV *P = (FTAR_GLOBAL PV *)packed;
+    size_t i = tid;
+    for (; i + (size_t)(kUnroll - 1) * nth < ng; i += (size_t)kUnroll * nth) {
+        if (SCATTER) {
+            PV v[kUnroll];
+#pragma unroll
+            for (int u = 0; u < kUnroll; u++) v[u] = P[i + (size_t)u * nth];
+#pragma unroll
+            for (int u = 0; u < kUnroll; u++) __builtin_nontemporal_store(narrow_group<T, K>(v[u], scale), U + i + (size_t)u * nth);
+        } else {
+            UV v[kUnroll];
+#pragma unroll
+            for (int u = 0; u < kUnroll; u++) v[u] = __builtin_nontemporal_load(U + i + (size_t)u * nth);
+#pragma unroll
+            for (int u = 0; u < kUnroll; u++) P[i + (size_t)u * nth] = widen_group<T, K>(v[u]);
+        }
+    }
+    for (; i < ng; i += nth) {
+        if (SCATTER) __builtin_nontemporal_store(narrow_group<T, K>(P[i], scale), U + i);
+        else P[i] = widen_group<T, K>(__builtin_nontemporal_load(U + i));
+    }
+}
+
+template <typename T, bool SCATTER>
+__device__ __forceinline__ void cvt_move_piece(const CPiece &P, char *packed, float scale, unsigned tid, unsigned nth)
+{
+    char *k = packed + P.poff;
+    cvt_groups<T, SCATTER, 1>(P.user, k, P.head, scale, tid, nth);
+    if (P.k == 1) return;
+    char *ub = P.user + 2 * P.head, *kb = k + 4 * P.head;
+    if (P.k == 8) cvt_groups<T, SCATTER, 8>(ub, kb, P.nvec, scale, tid, nth);
+    else if (P.k == 4) cvt_groups<T, SCATTER, 4>(ub, kb, P.nvec, scale, tid, nth);
+    else cvt_groups<T, SCATTER, 2>(ub, kb, P.nvec, scale, tid, nth);
+    const size_t done = P.head + P.nvec * P.k;
+    cvt_groups<T, SCATTER, 1>(P.user + 2 * done, k + 4 * done, P.n - done, scale, tid, nth);
+}
+
+// gather_kernel's grid, search and walk (tiles, offsets and kWavePiece in packed bytes)
+template <typename T, bool SCATTER>
+__global__ __launch_bounds__(kBlock) void gather_cvt_kernel(GatherArgs A, float scale)
+{
+    signal_acquire(A.sig);
+    const unsigned b0 = (unsigned)__builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    const unsigned nb = (unsigned)__builtin_amdgcn_readfirstlane((int)gridDim.x);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned lane = threadIdx.x & 63;
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) GEntry *CTab; // scalar loads, as gather_kernel's
+#else
+    typedef const GEntry *CTab;
+#endif
+    const CTab tab = (CTab)A.tab;
+    for (unsigned t = b0; t < A.ntiles; t += nb) {
+        const size_t lo = (size_t)t * kTileBytes;
+        const size_t hi = lo + kTileBytes < A.total ? lo + kTileBytes : A.total;
+        for (int e = __builtin_amdgcn_readfirstlane(gather_first(tab, A.n, lo)); e < A.n; e++) {
+            const GEntry E = {tab[e].ptr, tab[e].off, tab[e].bytes};
+            CPiece P;
+            if (!cvt_piece(E, lo, hi, A.packed, &P)) break;
+            const bool big = P.n * 4 >= kWavePiece; // the workgroup's piece, or one wave's
+            if (big || (e & 3) == wave) cvt_move_piece<T, SCATTER>(P, A.packed, scale, big ? threadIdx.x : lane, big ? kBlock : 64);
+            if (E.off + E.bytes >= hi) break;
+        }
+    }
+    signal_done(A.sig);
+}
+
+hipError_t launch_gather_cvt(const GatherArgs &A, int dtype, float scale, int scatter, unsigned grid, hipStream_t s)
+{
+    if (!A.packed || !A.tab || A.n < 1 || A.n > kMaxGather || grid == 0 || grid > A.ntiles || A.es != 4 || A.total % 4 ||
+        (size_t)A.ntiles != (A.total + kTileBytes - 1) / kTileBytes || (dtype != kFloat16 && dtype != kBFloat16))
+        return hipErrorInvalidValue;
+    if (dtype == kFloat16) {
+        if (scatter) hipLaunchKernelGGL((gather_cvt_kernel<f16_t, true>), dim3(grid), dim3(kBlock), 0, s, A, scale);
+        else hipLaunchKernelGGL((gather_cvt_kernel<f16_t, false>), dim3(grid), dim3(kBlock), 0, s, A, scale);
+    } else {
+        if (scatter) hipLaunchKernelGGL((gather_cvt_kernel<bf16_t, true>), dim3(grid), dim3(kBlock), 0, s, A, scale);
+        else hipLaunchKernelGGL((gather_cvt_kernel<bf16_t, false>), dim3(grid), dim3(kBlock), 0, s, A, scale);
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_segments(int dtype, int op, const KSegList &L, unsigned grid, hipStream_t s)
 {
     switch (dtype) {

@@ -15,9 +15,11 @@
  * ranks from 4 ranks on -- and its rank as the index; the check recomputes each element's winner
  * (the largest value, the lowest rank among equals) on the host.
  *
- * FTBENCH_MULTI=K (float32 only, 1 <= K <= min(count, FTAR_MULTI_MAX)): the job's `count` is split into
- * K buffers as equal as possible, each send and receive buffer a hipMalloc of its own, and every
- * call is one ftar_allreduce_multi over the list; the check and the output line are unchanged.
+ * FTBENCH_MULTI=K (float32, float16, bfloat16; 1 <= K <= min(count, FTAR_MULTI_MAX)): the job's `count` is
+ * split into K buffers as equal as possible, each send and receive buffer a hipMalloc of its own, and
+ * every call is one ftar_allreduce_multi over the list; the check and the output line are unchanged.
+ * FTBENCH_ACC32=1 (with FTBENCH_MULTI and a 16-bit type): the call is ftar_allreduce_multi_acc32 with
+ * scale 1 instead -- float32 accumulation; the sums are exact either way, so the check is the same.
  *
  * Every rank hipMallocs float32 send / receive vectors of `count` elements on its device,
  * fills the send vector with its original rank (the reference drivers' input,
@@ -81,7 +83,8 @@ static float from_f16(uint16_t h)
 }
 
 /* the 16-bit job: same schedule calls, same JSON line */
-static int run16(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev);
+static int run16(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev,
+                 int multi, int acc32);
 /* the pair-type job (MAXLOC) */
 static int runpair(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev);
 
@@ -118,11 +121,18 @@ int main(int argc, char **argv)
     CHECK_HIP(hipSetDevice(dev));
     const char *me = getenv("FTBENCH_MULTI");
     const int multi = me && *me ? atoi(me) : 0;
-    if (me && *me && (multi < 1 || multi > FTAR_MULTI_MAX || (size_t)multi > count || dt16 || dtpair)) {
-        fprintf(stderr, "ftbench: FTBENCH_MULTI=%s: 1 .. min(count, %d) buffers of float32\n", me, FTAR_MULTI_MAX);
+    if (me && *me && (multi < 1 || multi > FTAR_MULTI_MAX || (size_t)multi > count || dtpair)) {
+        fprintf(stderr, "ftbench: FTBENCH_MULTI=%s: 1 .. min(count, %d) buffers of f32, f16 or bf16\n", me,
+                FTAR_MULTI_MAX);
         return 2;
     }
-    if (dt16) return run16(rd, count, calls, (ftar_dtype)dt16, comm, wrank, wsize, dev);
+    const char *ae = getenv("FTBENCH_ACC32");
+    const int acc32 = ae && atoi(ae) != 0;
+    if (acc32 && !(multi && dt16)) {
+        fprintf(stderr, "ftbench: FTBENCH_ACC32 needs FTBENCH_MULTI and f16 or bf16\n");
+        return 2;
+    }
+    if (dt16) return run16(rd, count, calls, (ftar_dtype)dt16, comm, wrank, wsize, dev, multi, acc32);
     if (dtpair) return runpair(rd, count, calls, (ftar_dtype)dtpair, comm, wrank, wsize, dev);
 
     /* FTBENCH_PATTERN=1: x_r[i] = (7 i + 13 r) mod 4096 instead of r, so every element
@@ -215,7 +225,8 @@ int main(int argc, char **argv)
     return 0;
 }
 
-static int run16(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev)
+static int run16(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev,
+                 int multi, int acc32)
 {
     const char *pe = getenv("FTBENCH_PATTERN");
     const int pattern = pe && atoi(pe) != 0;
@@ -227,16 +238,36 @@ static int run16(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm
         h[i] = bf ? to_bf16(v) : to_f16(v);
     }
     uint16_t *s = NULL, *r = NULL;
-    CHECK_HIP(hipMalloc((void **)&s, count * sizeof(uint16_t)));
-    CHECK_HIP(hipMalloc((void **)&r, count * sizeof(uint16_t)));
-    CHECK_HIP(hipMemcpy(s, h, count * sizeof(uint16_t), hipMemcpyHostToDevice));
+    static const void *ms_[FTAR_MULTI_MAX];
+    static void *mr_[FTAR_MULTI_MAX];
+    static size_t mc_[FTAR_MULTI_MAX];
+    if (multi) {
+        size_t off = 0;
+        for (int k = 0; k < multi; k++) {
+            mc_[k] = count / (size_t)multi + ((size_t)k < count % (size_t)multi);
+            void *a = NULL;
+            CHECK_HIP(hipMalloc(&a, mc_[k] * sizeof(uint16_t)));
+            CHECK_HIP(hipMalloc(&mr_[k], mc_[k] * sizeof(uint16_t)));
+            CHECK_HIP(hipMemcpy(a, h + off, mc_[k] * sizeof(uint16_t), hipMemcpyHostToDevice));
+            ms_[k] = a;
+            off += mc_[k];
+        }
+    } else {
+        CHECK_HIP(hipMalloc((void **)&s, count * sizeof(uint16_t)));
+        CHECK_HIP(hipMalloc((void **)&r, count * sizeof(uint16_t)));
+        CHECK_HIP(hipMemcpy(s, h, count * sizeof(uint16_t), hipMemcpyHostToDevice));
+    }
     CHECK_HIP(hipDeviceSynchronize());
 
     double ms[MAX_CALLS], value[MAX_CALLS], hbm[MAX_CALLS];
     int rc[MAX_CALLS], rec[MAX_CALLS], size_after[MAX_CALLS], uniform[MAX_CALLS], step0_copy = 0;
     for (int c = 0; c < calls; c++) {
-        rc[c] = rd ? ftar_recursive_doubling(s, r, count, dt, FTAR_SUM, comm)
-                   : ftar_allreduce_rabenseifner(s, r, count, dt, FTAR_SUM, comm);
+        const ftar_algo al = rd ? FTAR_ALGO_RD : FTAR_ALGO_RABENSEIFNER;
+        if (acc32) rc[c] = ftar_allreduce_multi_acc32(al, ms_, mr_, mc_, multi, dt, FTAR_SUM, 1.0f, comm);
+        else if (multi) rc[c] = ftar_allreduce_multi(al, ms_, mr_, mc_, multi, dt, FTAR_SUM, comm);
+        else
+            rc[c] = rd ? ftar_recursive_doubling(s, r, count, dt, FTAR_SUM, comm)
+                       : ftar_allreduce_rabenseifner(s, r, count, dt, FTAR_SUM, comm);
         ftar_stats st;
         ftar_last_stats(comm, &st);
         ms[c] = st.wall_s * 1e3;
@@ -244,7 +275,13 @@ static int run16(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm
         rec[c] = st.recoveries;
         size_after[c] = st.comm_size_after;
         step0_copy |= st.step0_copy;
-        CHECK_HIP(hipMemcpy(h, r, count * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        if (multi) {
+            size_t off = 0;
+            for (int k = 0; k < multi; off += mc_[k], k++)
+                CHECK_HIP(hipMemcpy(h + off, mr_[k], mc_[k] * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        } else {
+            CHECK_HIP(hipMemcpy(h, r, count * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        }
         value[c] = bf ? from_bf16(h[0]) : from_f16(h[0]);
         uniform[c] = 1;
         const int members = size_after[c];
@@ -270,6 +307,10 @@ static int run16(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm
     printf("]}\n");
     fflush(stdout);
     ftar_finalize(comm);
+    for (int k = 0; k < multi; k++) {
+        (void)hipFree((void *)(uintptr_t)ms_[k]);
+        (void)hipFree(mr_[k]);
+    }
     (void)hipFree(s);
     (void)hipFree(r);
     free(h);

@@ -229,6 +229,44 @@ int ftar_allreduce_multi(ftar_algo algo, const void *const *sbufs, void *const *
                          const size_t *counts, int nbufs,
                          ftar_dtype dtype, ftar_op op, ftar_comm *comm);
 
+/* The list form for 2-byte floats with float32 ACCUMULATION: dtype is FTAR_FLOAT16 or
+ * FTAR_BFLOAT16 (a training job's fp16 / bf16 gradients).  ftar_allreduce_multi on such a list
+ * rounds every combination to 16 bits; here the result is exactly:
+ *   1. widen:  every element of the dense concatenation sbufs[0] ++ sbufs[1] ++ ... becomes a
+ *      float32 (exact, subnormals and +-0 included; a NaN stays a NaN, payload unspecified);
+ *   2. reduce: the plain FTAR_FLOAT32 Allreduce named by `algo` with `op` on that float32
+ *      vector -- "exactly" as above: the bits, the recovery and abort outcomes, the comm
+ *      re-targeting, the FTAR_KILL call index (one call) and the return code;
+ *   3. scale and narrow: every element a of the float32 result becomes narrow(scale * a): one
+ *      IEEE float32 multiplication (round to nearest even, subnormals kept), then ONE conversion
+ *      to dtype, round to nearest even (subnormals kept, overflow to +-inf, a NaN gives some
+ *      quiet NaN).  scale == 1.0f changes nothing;
+ *   4. scatter: the narrowed result is cut back into rbufs[i] at the same element offsets.
+ * The scale is applied whatever the op (SUM, PROD, MAX, MIN alike).  It is the caller's number:
+ * the library cannot know how many ranks will have contributed after a recovery (the result of a
+ * recovered call is the survivors'), so it does not guess a divisor -- pass 1.0f and divide by
+ * ftar_comm_size afterwards when an exact mean over the survivors is wanted.  An fp16 SUM that
+ * would pass 65504 stays finite in float32 and comes back in range with scale = 1 / ranks.
+ * The rules are ftar_allreduce_multi's -- collective, per-entry in place allowed, outputs pairwise
+ * disjoint, an output may overlap another entry's input (all inputs are read before any output is
+ * written), counts[i] == 0 entries skipped unlooked-at -- except:
+ *   - entries need 2-byte alignment only;
+ *   - there is no straight-through case: one non-empty entry is staged like any other (the
+ *     conversion has to happen); a total of 0 elements returns what the plain FTAR_FLOAT32 call
+ *     with count == 0 returns;
+ *   - ftar_stats.coalesced is the number of non-empty entries (>= 1).
+ * The op / dtype check comes first and keeps its codes (a logical or bitwise op or MAXLOC on a
+ * 2-byte float: FTAR_ERR_OP).  Then FTAR_ERR_ARG, before anything is launched or any barrier
+ * entered: a dtype other than the two (float32 lists: ftar_allreduce_multi), a scale that is not
+ * finite, comm, sbufs, rbufs or counts NULL, nbufs < 1 or > FTAR_MULTI_MAX, an unknown algo, two
+ * overlapping outputs, a non-empty buffer the device entry points would refuse or one at an odd
+ * address.  If the schedule returns an error no rbufs[i] is written.
+ * Costs 2 x 4 bytes x the largest total so far in device memory (the float32 staging), and twice
+ * the bytes of ftar_allreduce_multi on the links. */
+int ftar_allreduce_multi_acc32(ftar_algo algo, const void *const *sbufs, void *const *rbufs,
+                               const size_t *counts, int nbufs,
+                               ftar_dtype dtype, ftar_op op, float scale, ftar_comm *comm);
+
 /* MPI_Reduce_local(in, inout, count, dtype, op) on the device:
  * inout[i] = in[i] (op) inout[i] with the reference's operand roles.
  * `stream` is a hipStream_t (NULL = null stream); the call is asynchronous.
