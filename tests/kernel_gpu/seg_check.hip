@@ -11,6 +11,19 @@
 // infinities.  Every byte around each destination is checked untouched.
 //   seg_check [lists [swapped]]   prints one line per failing list, then "seg_check: N lists, F failed";
 //   `swapped` expects y op x -- the checker's own test: float MAX / MIN lists must then fail
+//
+//   seg_check types [swapped]   the same on the element types the oracle does not know (element
+//   sizes 2, 8 and 16): 210 lists, float16 / bfloat16 x SUM, PROD, MAX, MIN and the three pair
+//   types x MAXLOC, MINLOC in rotation, against the plain reference of ref_types.h on the inputs
+//   of gen_types.h; windows at every offset past a 16-byte boundary the type's alignment allows
+//   (heads of 7, 5 and 1 two-byte elements; 8-byte pairs at 4 and 12: co-aligned, yet the scalar
+//   path), co-aligned or independent; one piece in eight 256 KiB .. 2 MiB, and three lists
+//   per combination built to reach the interleaved prefix (counted per element size, each must
+//   occur); the four grid caps.  One device
+//   arena serves every list.  Destinations bit for bit (NaN-ness where a SUM / PROD expectation
+//   is a NaN), every other byte of the arena -- guards and sources -- untouched.  Prints
+//   "seg_check types: N lists, F failed"; `swapped` succeeds when exactly the order-sensitive
+//   lists with a reduce piece of n >= 257 fail and every SUM / PROD and FTAR_2INT list passes.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -22,6 +35,7 @@
 #include <vector>
 
 #include "ftar_kernels.h"
+#include "gen_types.h"
 
 extern "C" int ftar_oracle_reduce_local(int dtype, int op, const void *in, void *inout, size_t n);
 
@@ -80,8 +94,11 @@ static Buf alloc(size_t bytes, size_t off, unsigned char fillbyte)
     return b;
 }
 
+int types_main(bool swapped);
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "types")) return types_main(argc > 2 && !strcmp(argv[2], "swapped"));
     const int lists = argc > 1 ? atoi(argv[1]) : 400;
     const bool swapped = argc > 2 && !strcmp(argv[2], "swapped");
     std::mt19937_64 g(4242);
@@ -178,4 +195,148 @@ int main(int argc, char **argv)
     }
     printf("seg_check: %d lists, %d failed\n", lists, failed);
     return failed ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------
+// `types`: float16, bfloat16 and the pair types (gen_types.h's lists, ref_types.h's reference)
+// ---------------------------------------------------------------------------------
+static_assert(kref::kFloat16 == ftar::kFloat16 && kref::kBFloat16 == ftar::kBFloat16 && kref::kFloatInt == ftar::kFloatInt &&
+                  kref::k2Int == ftar::k2Int && kref::kDoubleInt == ftar::kDoubleInt && kref::kSum == ftar::kSum &&
+                  kref::kProd == ftar::kProd && kref::kMax == ftar::kMax && kref::kMin == ftar::kMin &&
+                  kref::kMaxloc == ftar::kMaxloc && kref::kMinloc == ftar::kMinloc,
+              "ref_types.h's numbers are the product's");
+
+namespace {
+
+constexpr size_t kGuard = 64;
+inline size_t slot_size(size_t bytes) { return (bytes + 16 + 2 * kGuard + 255) & ~(size_t)255; }
+
+// a piece's four slots in the arena: x, y, out, out2, each 256-byte aligned, the operand kGuard
+// bytes and its window offset past the slot's start
+struct Placed {
+    size_t at[4], bytes;
+    size_t pos(int which, int off) const { return at[which] + kGuard + (size_t)off; }
+};
+
+size_t place(const kgen::SegList &L, std::vector<Placed> *out)
+{
+    size_t next = 0;
+    for (const kgen::SegPiece &P : L.pc) {
+        Placed pl;
+        pl.bytes = P.n * kref::esize(L.dt);
+        for (int w = 0; w < 4; w++) {
+            pl.at[w] = next;
+            next += slot_size(pl.bytes);
+        }
+        if (out) out->push_back(pl);
+    }
+    return next;
+}
+
+} // namespace
+
+int types_main(bool swapped)
+{
+    size_t arena = 0;
+    for (int li = 0; li < kgen::kSegLists; li++) arena = std::max(arena, place(kgen::seg_list(li), nullptr));
+    unsigned char *dev;
+    CHK(hipMalloc((void **)&dev, arena));
+    std::vector<unsigned char> img(arena), back(arena);
+    int failed = 0, must = 0, must_failed = 0, free_failed = 0, interleaved[3] = {0, 0, 0}; // by element size 2, 8, 16
+    for (int li = 0; li < kgen::kSegLists; li++) {
+        const kgen::SegList G = kgen::seg_list(li);
+        const kgen::Combo combo{G.dt, G.op};
+        const size_t es = kref::esize(G.dt);
+        const int nseg = (int)G.pc.size();
+        std::vector<Placed> pl;
+        const size_t used = place(G, &pl);
+        if (used > arena) return 2;
+        std::vector<ftar::SegIn> in(nseg);
+        std::vector<kgen::Bytes> want(nseg);
+        bool judged = false; // a reduce piece long enough for the inputs to show the operand order
+        for (int s = 0; s < nseg; s++) {
+            const kgen::SegPiece &P = G.pc[s];
+            const Placed &p = pl[s];
+            const int offs[4] = {P.ox, P.oy, P.oo, P.oo2};
+            const unsigned char fillbyte[4] = {0x33, 0x33, 0xA5, 0x5A};
+            for (int w = 0; w < 4; w++) memset(&img[p.at[w]], fillbyte[w], slot_size(p.bytes));
+            kgen::Bytes x(p.bytes), y(p.bytes);
+            kgen::fill(x.data(), G.dt, G.op, P.n, 0, 2, P.seed);
+            kgen::fill(y.data(), G.dt, G.op, P.n, 1, 2, P.seed);
+            memcpy(&img[p.pos(0, offs[0])], x.data(), p.bytes);
+            memcpy(&img[p.pos(1, offs[1])], y.data(), p.bytes);
+            in[s].kind = P.kind ? ftar::kReduce : ftar::kCopy;
+            in[s].x = dev + p.pos(0, offs[0]);
+            in[s].y = P.kind ? dev + p.pos(1, offs[1]) : nullptr;
+            in[s].out = dev + p.pos(2, offs[2]);
+            in[s].out2 = P.with2 ? dev + p.pos(3, offs[3]) : nullptr;
+            in[s].n = P.n;
+            if (!P.kind) {
+                want[s] = x;
+                continue;
+            }
+            judged |= P.n >= 257;
+            want[s] = swapped ? y : x; // out = x op y: the reference's inout is x, its in is y
+            if (kref::reduce_local(G.dt, G.op, (swapped ? x : y).data(), want[s].data(), P.n) != 0) {
+                fprintf(stderr, "reference refused dtype %d op %d\n", G.dt, G.op);
+                return 2;
+            }
+        }
+        ftar::KSegList L;
+        const unsigned grid = ftar::plan_segments(in.data(), nseg, es, G.cap, &L);
+        L.nt_store = (unsigned)(kgen::mix((uint64_t)li) >> 7) & 1;
+        memset(&L.sig, 0, sizeof(L.sig));
+        bool ok = grid != 0;
+        if (!ok) printf("FAIL list %d: plan_segments refused (%d pieces, cap %u)\n", li, nseg, G.cap);
+        if (ok) {
+            interleaved[es == 2 ? 0 : es == 8 ? 1 : 2] += L.il_blocks > 0;
+            CHK(hipMemcpy(dev, img.data(), used, hipMemcpyHostToDevice));
+            CHK(ftar::launch_segments(G.dt, G.op, L, grid, 0));
+            CHK(hipDeviceSynchronize());
+            CHK(hipMemcpy(back.data(), dev, used, hipMemcpyDeviceToHost));
+        }
+        for (int s = 0; s < nseg && ok; s++) {
+            const kgen::SegPiece &P = G.pc[s];
+            const Placed &p = pl[s];
+            const int offs[4] = {P.ox, P.oy, P.oo, P.oo2};
+            for (int w = 0; w < 4 && ok; w++) {
+                const bool dest = w == 2 || (w == 3 && P.with2);
+                const size_t a = p.at[w], b = dest ? p.pos(w, offs[w]) : a + slot_size(p.bytes), e = a + slot_size(p.bytes);
+                // sources, unused slots and the bytes around a destination: as uploaded
+                if (memcmp(&back[a], &img[a], b - a) || (dest && memcmp(&back[b + p.bytes], &img[b + p.bytes], e - b - p.bytes))) {
+                    printf("FAIL list %d piece %d/%d: %s written\n", li, s, nseg,
+                           dest ? "bytes outside a destination" : "a source or an unused destination");
+                    ok = false;
+                }
+                size_t first = 0;
+                if (ok && dest && kgen::count_diff(&back[b], want[s].data(), G.dt, G.op, P.n, &first)) {
+                    printf("FAIL list %d piece %d/%d (%s, n %zu, dtype %d op %d, cap %u, offsets %d %d %d %d, %s): element %zu\n", li,
+                           s, nseg, P.kind ? "reduce" : "copy", P.n, G.dt, G.op, G.cap, P.ox, P.oy, P.oo, P.oo2,
+                           w == 3 ? "second destination" : "out", first);
+                    ok = false;
+                }
+            }
+        }
+        failed += !ok;
+        if (kgen::order_sensitive(combo) && judged) {
+            must++;
+            must_failed += !ok;
+        } else if (!kgen::order_sensitive(combo)) {
+            free_failed += !ok;
+        }
+    }
+    CHK(hipFree(dev));
+    if (!swapped) {
+        printf("seg_check types: lists with an interleaved prefix: %d / %d / %d at element size 2 / 8 / 16\n", interleaved[0],
+               interleaved[1], interleaved[2]);
+        if (!interleaved[0] || !interleaved[1] || !interleaved[2]) {
+            printf("FAIL an element size never reached the interleaved prefix\n");
+            failed++;
+        }
+        printf("seg_check types: %d lists, %d failed\n", kgen::kSegLists, failed);
+        return failed ? 1 : 0;
+    }
+    printf("seg_check types swapped: %d lists, %d failed; order-sensitive with a reduce piece of n >= 257: %d of %d failed; "
+           "order-free: %d failed\n", kgen::kSegLists, failed, must_failed, must, free_failed);
+    return (must_failed == must && free_failed == 0) ? 0 : 1;
 }

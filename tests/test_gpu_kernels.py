@@ -319,3 +319,27 @@ def test_segment_kernel_against_oracle():
     workgroups -- bit-exact against the oracle, nothing written outside a destination,
     sources untouched; MAX / MIN over NaN, signed zeros and infinities."""
     _run_checker("seg_check")
+
+
+def test_tree_kernels_on_half_and_pair_types():
+    """tree_check types: tree_kernel and tree_batch_kernel on float16 / bfloat16 (SUM, PROD, MAX,
+    MIN) and the three pair types (MAXLOC, MINLOC), which the oracle does not know -- against the
+    plain reference of tests/kernel_gpu/ref_types.h (pinned against torch's CPU arithmetic and
+    numpy in test_kernel_ref.py, where the inputs are also shown to tell a wrong rounding or
+    operand order from the right one).  p = 2, 4, 8 and 16, unroll 1 / 2 / 4, extra destinations,
+    both kinds of store, lengths around every boundary of the 2-, 8- and 16-byte elements, heads
+    of 7, 5 and 1 elements, 8-byte pairs 4 and 12 bytes past a 16-byte boundary (co-aligned, yet
+    the scalar path), mutually misaligned sources; batches of 1 / 3 / 8 trees, capped to 64 / 9
+    workgroups.  Bit for bit, NaN-ness where a SUM / PROD expectation is a NaN; guards, sources
+    and extra destinations checked."""
+    _run_checker("tree_check", "types")
+
+
+def test_segment_kernel_on_half_and_pair_types():
+    """seg_check types: 210 lists of up to 16 copy / reduce pieces at element sizes 2, 8 and 16
+    (the same 14 type / op combinations in rotation), windows co-aligned or independent at
+    every offset the types' alignment allows, pieces of up to 2 MiB (the interleaved 128 KiB
+    prefix, required to occur at every element size), a second destination, grids capped at
+    2^20 / 1024 / 128 / 7 workgroups -- against the same reference, every byte outside a
+    destination untouched."""
+    _run_checker("seg_check", "types")

@@ -321,7 +321,7 @@ def test_schedule_against_oracle(oracle, cid, algo, p, nbytes, settings, kill, n
 def test_inplace_and_offset(oracle):
     """sbuf == rbuf and windows at byte offset 8 (a one-element head for the 8-byte types, the
     scalar path for the 16-byte type) at p = 4: the tree form in one job, the one-shot and gated
-    recursive-doubling forms in another."""
+    recursive-doubling forms in another; the 8-byte types' windows at 4 and 12 in a third."""
     calls = [call("float_int", "raben", MAXLOC, inplace=1), call("double_int", "raben", MINLOC, offset=8),
              call("double_int", "rd", MAXLOC, inplace=1, offset=8), call("2int", "rd", MINLOC, offset=8)]
     data = [keyed_inputs(c["dtype"], 4, count_of(2 * 65541, c["dtype"]), seed=60 + k) for k, c in enumerate(calls)]
@@ -338,6 +338,18 @@ def test_inplace_and_offset(oracle):
     assert cp.returncode == 0, cp.stderr[-3000:]
     for k, c in enumerate(calls):
         check_against_oracle(oracle, c["dtype"], c["algo"], c["op"], data[k], [], outs[k], stats[k], cp, ("small", k))
+    # the alignment the header allows the 8-byte pair types: windows 4 and 12 bytes past a 16-byte
+    # boundary -- co-aligned, yet no element sits on a vector boundary: the scalar path.  Both
+    # types at the one-shot size (its gated launch stages the unaligned input element by element)
+    # and at the tree size, in one job with the one-shot limit between the two
+    calls = [call("float_int", "raben", MINLOC, offset=4), call("2int", "raben", MAXLOC, offset=12),
+             call("2int", "raben", MINLOC, offset=4), call("float_int", "raben", MAXLOC, inplace=1, offset=12)]
+    sizes = [2 * 4099, 2 * 4099, 2 * 65541, 2 * 65541]
+    data = [keyed_inputs(c["dtype"], 4, count_of(sizes[k], c["dtype"]), seed=90 + k) for k, c in enumerate(calls)]
+    cp, outs, stats = run_job(calls, data, 4, {"FTAR_ONESHOT_MAX": str(64 << 10)})
+    assert cp.returncode == 0, cp.stderr[-3000:]
+    for k, c in enumerate(calls):
+        check_against_oracle(oracle, c["dtype"], c["algo"], c["op"], data[k], [], outs[k], stats[k], cp, ("4 mod 8", k))
 
 
 def test_host_buffers(oracle):

@@ -1,0 +1,141 @@
+"""The plain reference behind tree_check's and seg_check's `types` matrices
+(tests/kernel_gpu/ref_types.h), pinned on the CPU, and the self-test of those matrices' inputs.
+
+tests/kernel_gpu/ref_check is a host program (no HIP call): `apply` runs the reference over
+operand files, `selftest` generates the inputs of every GPU case and asserts that they can tell
+a wrong kernel from a right one (a wrong rounding, flushed subnormals, swapped operands; the
+conditions are listed in ref_check.cpp).  Both also run in a build with ASan + UBSan.
+
+References here
+* float16 / bfloat16: torch CPU arithmetic in the element type (test_gpu_half.pair), on every
+  16-bit pattern against 48 partners: 16 special values as `in`, the same as `inout`, and 16
+  rotations of the pattern table;
+* pair types: include/ftar.h's rule in numpy on structured arrays (test_gpu_pair.loc), on
+  test_gpu_pair's special and random pairs.
+"""
+import fcntl
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from test_gpu_half import SUM, PROD, MAX, MIN, TD, bits, pair, to_f32
+from test_gpu_pair import MAXLOC, MINLOC, ST, fill_padding, loc, random_pairs, raw, special_pairs
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DIR = os.path.join(ROOT, "tests", "kernel_gpu")
+DTYPE = {"f16": 16, "bf16": 17, "float_int": 32, "2int": 33, "double_int": 34}
+
+
+@pytest.fixture(scope="module")
+def ref_check(oracle):
+    """(plain, sanitized) builds of the program; the oracle library they pass the old types to
+    is built by the `oracle` fixture."""
+    os.makedirs(os.path.join(DIR, "_build"), exist_ok=True)
+    with open(os.path.join(DIR, "_build", ".ref.lock"), "w") as lk:  # one build at a time (pytest-xdist workers)
+        fcntl.flock(lk, fcntl.LOCK_EX)
+        subprocess.run(["make", "-s", "-C", DIR, "ref"], check=True)
+    plain, san = os.path.join(DIR, "_build", "ref_check"), os.path.join(DIR, "_build", "ref_check_san")
+    syms = subprocess.run(["nm", san], capture_output=True, text=True, check=True).stdout
+    assert "__asan_init" in syms and "__ubsan_handle" in syms  # really built with the sanitizers
+    return plain, san
+
+
+def apply(exe, tmp, dtype, op, inout, in_):
+    """inout <op> in over raw byte buffers, by the program."""
+    fi, fio, fo = (os.path.join(tmp, n) for n in ("in.bin", "inout.bin", "out.bin"))
+    raw(in_).tofile(fi)
+    raw(inout).tofile(fio)
+    cp = subprocess.run([exe, "apply", str(DTYPE[dtype]), str(op), fi, fio, fo], capture_output=True, text=True, timeout=300)
+    assert cp.returncode == 0, cp.stdout + cp.stderr[-3000:]
+    return np.fromfile(fo, dtype=np.uint8)
+
+
+def half_operands(name):
+    """(inout, in): every 16-bit pattern against 48 partners."""
+    import torch
+    fi = torch.finfo(TD[name])
+    sub = fi.smallest_normal * fi.eps  # the smallest subnormal
+    inf, nan = float("inf"), float("nan")
+    sp = bits(torch.tensor([0.0, -0.0, sub, -sub, 1.0, -1.0, fi.max, -fi.max, inf, -inf, nan, fi.smallest_normal,
+                            fi.eps / 2, 0.5, 1.5, 2.0], dtype=torch.float64).to(TD[name]))
+    assert sp.size == 16 and (sp[2], sp[3]) == (0x0001, 0x8001) and sp[8] == (0x7C00 if name == "f16" else 0x7F80)
+    pat = np.arange(1 << 16, dtype=np.uint16)
+    xs, ys = [], []
+    for s in sp:
+        const = np.full(pat.size, s, dtype=np.uint16)
+        xs += [pat, const]
+        ys += [const, pat]
+    for k in range(16):
+        xs.append(pat)
+        ys.append(np.roll(pat, 4099 * (k + 1) + (1 << 11) * k))
+    return np.concatenate(xs), np.concatenate(ys)
+
+
+@pytest.mark.parametrize("name", ["f16", "bf16"])
+def test_reference_matches_torch_on_every_pattern(ref_check, name):
+    """SUM and PROD: the correctly rounded result bit for bit, NaN where torch has a NaN.  MAX and
+    MIN: the chosen operand's own bits, NaN payloads included."""
+    x, y = half_operands(name)
+    assert x.size == 48 * (1 << 16)
+    with tempfile.TemporaryDirectory(prefix="ftar_ref_") as tmp:
+        for op in (SUM, PROD, MAX, MIN):
+            want = pair(name, op)(x, y)
+            got = apply(ref_check[0], tmp, name, op, x, y).view(np.uint16)
+            assert got.shape == want.shape
+            if op in (SUM, PROD):
+                nan_w, nan_g = np.isnan(to_f32(want, name)), np.isnan(to_f32(got, name))
+                assert np.array_equal(nan_w, nan_g), (name, op, np.flatnonzero(nan_w != nan_g)[:8])
+                bad = np.flatnonzero((got != want) & ~nan_w)
+            else:
+                bad = np.flatnonzero(got != want)
+            assert bad.size == 0, (name, op, bad[:8], x[bad[:8]], y[bad[:8]], got[bad[:8]], want[bad[:8]])
+
+
+@pytest.mark.parametrize("name", ["float_int", "2int", "double_int"])
+def test_reference_matches_the_header_rule_on_pairs(ref_check, name):
+    rng = np.random.default_rng(77)
+    sx, sy = special_pairs(name)
+    x = np.concatenate([fill_padding(sx, rng), random_pairs(rng, 20011, name)])
+    y = np.concatenate([fill_padding(sy, rng), random_pairs(rng, 20011, name)])
+    with tempfile.TemporaryDirectory(prefix="ftar_ref_") as tmp:
+        for op in (MAXLOC, MINLOC):
+            want = raw(loc(op)(x, y))
+            got = apply(ref_check[0], tmp, name, op, x, y)
+            bad = np.flatnonzero((got.reshape(x.size, -1) != want.reshape(x.size, -1)).any(axis=1))
+            assert bad.size == 0, (name, op, bad[:8], x[bad[:8]], y[bad[:8]])
+
+
+def test_inputs_tell_a_wrong_kernel_from_a_right_one(ref_check):
+    """ref_check selftest: the conditions on the inputs of every case of the GPU matrices."""
+    cp = subprocess.run([ref_check[0], "selftest"], capture_output=True, text=True, timeout=600)
+    assert cp.returncode == 0, cp.stdout[-3000:] + cp.stderr[-3000:]
+    assert cp.stdout.rstrip().endswith("selftest: 0 failed"), cp.stdout[-3000:]
+    print(cp.stdout)
+
+
+def test_reference_under_sanitizers(ref_check):
+    """The same program built with ASan + UBSan: the reference over operands that reach every
+    branch of the rounding (specials against every pattern), and the whole self-test."""
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1")
+    pat = np.arange(1 << 16, dtype=np.uint16)
+    with tempfile.TemporaryDirectory(prefix="ftar_ref_") as tmp:
+        for name in ("f16", "bf16"):
+            for op in (SUM, PROD, MAX, MIN):
+                y = np.roll(pat, 4099 + op)
+                plain = apply(ref_check[0], tmp, name, op, pat, y)
+                fi, fio, fo = (os.path.join(tmp, n) for n in ("in.bin", "inout.bin", "out_san.bin"))
+                cp = subprocess.run([ref_check[1], "apply", str(DTYPE[name]), str(op), fi, fio, fo], capture_output=True,
+                                    text=True, timeout=300, env=env)
+                assert cp.returncode == 0, cp.stdout + cp.stderr[-3000:]
+                assert np.array_equal(np.fromfile(fo, dtype=np.uint8), plain)
+        rng = np.random.default_rng(5)
+        for name in ST:
+            x, y = random_pairs(rng, 4099, name), random_pairs(rng, 4099, name)
+            plain = apply(ref_check[0], tmp, name, MAXLOC, x, y)
+            assert np.array_equal(apply(ref_check[1], tmp, name, MAXLOC, x, y), plain)
+    cp = subprocess.run([ref_check[1], "selftest"], capture_output=True, text=True, timeout=900, env=env)
+    assert cp.returncode == 0, cp.stdout[-3000:] + cp.stderr[-3000:]
+    assert cp.stdout.rstrip().endswith("selftest: 0 failed"), cp.stdout[-3000:]
