@@ -14,6 +14,30 @@
 //       * in no SUM / PROD case more than 1/8 of the expected elements are NaN (compared by
 //         NaN-ness only), and at least half are finite and non-zero.
 //     A case is one tree (tree_kernel case, tree of a batch) or one reduce piece of a list.
+//       Then the tables of gather_check and the cases of lds_check (gen_movers.h):
+//       * every table is replayed with the product's own host functions (gather_first, gather_piece,
+//         cvt_piece of ftar_kernels.h; the arenas modelled as 256-byte aligned constants) at the
+//         three grids, and what the matrices are meant to reach is counted -- every unit of the
+//         plain mover, vector pieces with head, body and tail, pieces that are not vector pieces,
+//         small pieces on each of the four waves, the unrolled loops and their remainders and exact
+//         ends, tiles ending inside an entry and exactly at one's end, workgroups with two tiles
+//         and more, the converting classes 8, 4, 2 with head and tail and class 1.  Every count
+//         that the kernels can reach must be non-zero (the plain mover's one-wave pieces hold at
+//         most 63 vectors: its unrolled loop needs the workgroup).  The replay is accounting only:
+//         gather_check's expectation is plain concatenation.
+//       * every converting scatter case (table x type x scale) of 257 elements and more at a scale
+//         other than 0 expects at least one element that rounding toward zero, ties away from zero
+//         or flushed subnormals would get wrong, and at the scales whose product is not exact in
+//         float32 one that a single rounding of the exact product (a fused multiply-convert) would;
+//         over the matrix, a +0 for a zero product and an infinity for a NaN whose upper 16 bits
+//         read as one are seen, and -0 is expected both in elements that move one by one and in
+//         elements of a packed group, for both types;
+//       * in no such case (the block of infinities and NaNs apart) more than 1/8 of the expected
+//         elements are NaN, and at least half are finite and non-zero except at scale 0;
+//       * every order-sensitive lds_check case expects, in its full tiles and in its ragged rest
+//         alike (where they hold 257 elements or more), a byte that swapped operands would change.
+//   ref_check narrow DTYPE IN OUT   OUT = the float32 file IN narrowed once (the reference of the
+//       converting scatter at scale 1), 2 bytes per element
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -22,6 +46,8 @@
 #include <tuple>
 #include <vector>
 
+#include "ftar_kernels.h"
+#include "gen_movers.h"
 #include "gen_types.h"
 
 using namespace kgen;
@@ -127,6 +153,266 @@ static void judge(Stats &S, const char *what, int dt, int op, int p, size_t n, u
     }
 }
 
+// ---------------------------------------------------------------------------------
+// the movers' tables (gather_check) and the LDS reduce's cases (lds_check)
+// ---------------------------------------------------------------------------------
+namespace {
+using namespace kmov;
+
+const uintptr_t kDevBase = ((uintptr_t)1 << 40) + (size_t)ftar::kMaxGather * sizeof(ftar::GEntry); // 256-byte aligned
+const uintptr_t kHostBase = (uintptr_t)3 << 40;
+
+struct Loops { // one strided loop pair of move_piece / cvt_groups, by thread count (64: index 0, 256: index 1)
+    size_t unrolled[2] = {0, 0}, rest[2] = {0, 0}, end_m1[2] = {0, 0}, end_0[2] = {0, 0}, end_p1[2] = {0, 0};
+    void add(size_t n, unsigned nth)
+    {
+        const int w = nth == 256;
+        unrolled[w] += n > 3 * (size_t)nth;      // thread 0 enters the loop of kUnroll = 4
+        rest[w] += n % (4 * (size_t)nth) != 0;   // some thread has an element left behind it
+        end_m1[w] += n == 4 * (size_t)nth - 1;
+        end_0[w] += n == 4 * (size_t)nth;
+        end_p1[w] += n == 4 * (size_t)nth + 1;
+    }
+};
+
+struct Cover {
+    size_t pieces = 0, unit[4] = {0, 0, 0, 0}, vec_hbt = 0, nonvec = 0, small_wave[4] = {0, 0, 0, 0}, big = 0;
+    size_t tile_inside = 0, tile_at_end = 0, wg_two_tiles = 0;
+    size_t cls_ht[4] = {0, 0, 0, 0}; // classes 8, 4, 2 with head, body and tail; class 1
+    Loops loops;
+};
+
+std::vector<ftar::GEntry> entries(const Table &T, const Layout &L)
+{
+    std::vector<ftar::GEntry> tab(T.cnt.size());
+    for (size_t e = 0; e < tab.size(); e++)
+        tab[e] = ftar::GEntry{(void *)((T.pinned ? kHostBase : kDevBase) + L.user_at[e]), L.off[e], T.cnt[e] * T.es};
+    return tab;
+}
+
+// the kernels' walk; `path` (converting tables): 1 where an element moves alone, 2 in a group
+int replay(const Table &T, unsigned grid, Cover &C, std::vector<unsigned char> *path)
+{
+    const Layout L = layout(T);
+    const std::vector<ftar::GEntry> tab = entries(T, L);
+    const char *packed = (const char *)(kDevBase + L.packed_at);
+    const int n = (int)tab.size();
+    const unsigned ntiles = (unsigned)((L.total + ftar::kTileBytes - 1) / ftar::kTileBytes);
+    std::vector<unsigned char> cnt(L.total / T.es, 0);
+    for (unsigned b = 0; b < grid; b++) {
+        unsigned mine = 0;
+        for (unsigned t = b; t < ntiles; t += grid, mine++) {
+            const size_t lo = (size_t)t * ftar::kTileBytes, hi = lo + ftar::kTileBytes < L.total ? lo + ftar::kTileBytes : L.total;
+            for (int e = ftar::gather_first(tab.data(), n, lo); e < n; e++) {
+                size_t poff, bytes;
+                if (T.cvt) {
+                    ftar::CPiece P;
+                    if (!ftar::cvt_piece(tab[e], lo, hi, packed, &P)) break;
+                    poff = P.poff;
+                    bytes = P.n * 4;
+                    const unsigned nth = bytes >= kWave ? 256 : 64;
+                    const size_t tail = P.k == 1 ? 0 : P.n - P.head - P.nvec * P.k;
+                    C.cls_ht[P.k == 8 ? 0 : P.k == 4 ? 1 : P.k == 2 ? 2 : 3] += P.k == 1 || (P.head && P.nvec && tail);
+                    C.loops.add(P.head, nth);
+                    if (P.k > 1) {
+                        C.loops.add(P.nvec, nth);
+                        C.loops.add(tail, nth);
+                    }
+                    if (path)
+                        for (size_t i = 0; i < P.n; i++)
+                            (*path)[poff / 4 + i] = (P.k == 1 || i < P.head || i >= P.head + P.nvec * P.k) ? 1 : 2;
+                } else {
+                    ftar::GPiece P;
+                    if (!ftar::gather_piece(tab[e], lo, hi, packed, T.es, &P)) break;
+                    poff = P.poff;
+                    bytes = P.bytes;
+                    C.unit[P.unit == 1 ? 0 : P.unit == 2 ? 1 : P.unit == 4 ? 2 : 3]++;
+                    C.vec_hbt += P.vec && P.head && P.nvec && P.bytes - P.head - 16 * P.nvec;
+                    C.nonvec += !P.vec;
+                    if (P.vec) C.loops.add(P.nvec, bytes >= kWave ? 256 : 64);
+                }
+                C.pieces++;
+                if (bytes >= kWave) C.big++;
+                else C.small_wave[e & 3]++;
+                for (size_t i = 0; i < bytes / T.es; i++) cnt[poff / T.es + i]++;
+                if (tab[e].off + tab[e].bytes >= hi) {
+                    if (tab[e].off + tab[e].bytes > hi) C.tile_inside++;
+                    else if (e + 1 < n) C.tile_at_end++;
+                    break;
+                }
+            }
+        }
+        C.wg_two_tiles += mine >= 2;
+    }
+    for (unsigned char c : cnt)
+        if (c != 1) {
+            printf("FAIL %s grid %u: an element is covered %d times by the replay\n", T.name.c_str(), grid, c);
+            return 1;
+        }
+    return 0;
+}
+
+int need(const char *what, size_t v)
+{
+    if (v) return 0;
+    printf("FAIL the movers' tables never reach: %s\n", what);
+    return 1;
+}
+
+int movers_selftest()
+{
+    int failed = 0;
+    // ---- coverage ----
+    Cover P, V;
+    size_t nplain = 0, ncvt = 0, pinned[2] = {0, 0};
+    for (const Table &T : plain_tables()) {
+        nplain++;
+        pinned[0] += T.pinned;
+        const Layout L = layout(T);
+        for (unsigned g : grids((unsigned)((L.total + kTile - 1) / kTile))) failed += replay(T, g, P, nullptr);
+    }
+    const std::vector<Table> ctab = cvt_tables();
+    std::vector<std::vector<unsigned char>> paths;
+    for (const Table &T : ctab) {
+        ncvt++;
+        pinned[1] += T.pinned;
+        const Layout L = layout(T);
+        paths.emplace_back(T.elems(), 0);
+        bool first = true;
+        for (unsigned g : grids((unsigned)((L.total + kTile - 1) / kTile))) {
+            failed += replay(T, g, V, first ? &paths.back() : nullptr);
+            first = false;
+        }
+    }
+    printf("selftest: %zu plain tables (%zu pinned), %zu converting tables (%zu pinned); each runs in both directions\n", nplain,
+           pinned[0], ncvt, pinned[1]);
+    printf("selftest: plain: %zu pieces; unit 1 / 2 / 4 / 8: %zu / %zu / %zu / %zu; vector pieces with head, body and tail %zu, "
+           "not vector %zu\n", P.pieces, P.unit[0], P.unit[1], P.unit[2], P.unit[3], P.vec_hbt, P.nonvec);
+    printf("selftest: plain: small pieces on wave 0 / 1 / 2 / 3: %zu / %zu / %zu / %zu, the workgroup's %zu; tiles ending inside an "
+           "entry %zu, at an entry's end %zu; workgroups with >= 2 tiles %zu\n", P.small_wave[0], P.small_wave[1], P.small_wave[2],
+           P.small_wave[3], P.big, P.tile_inside, P.tile_at_end, P.wg_two_tiles);
+    printf("selftest: plain: unrolled loop entered at 64 / 256 threads: %zu / %zu, remainder: %zu / %zu; nvec = 4 * 256 - 1 / + 0: "
+           "%zu / %zu\n", P.loops.unrolled[0], P.loops.unrolled[1], P.loops.rest[0], P.loops.rest[1], P.loops.end_m1[1], P.loops.end_0[1]);
+    printf("selftest: converting: %zu pieces; class 8 / 4 / 2 with head, groups and tail: %zu / %zu / %zu, class 1: %zu\n", V.pieces,
+           V.cls_ht[0], V.cls_ht[1], V.cls_ht[2], V.cls_ht[3]);
+    printf("selftest: converting: small pieces on wave 0 / 1 / 2 / 3: %zu / %zu / %zu / %zu, the workgroup's %zu; tiles ending inside "
+           "an entry %zu, at an entry's end %zu; workgroups with >= 2 tiles %zu\n", V.small_wave[0], V.small_wave[1], V.small_wave[2],
+           V.small_wave[3], V.big, V.tile_inside, V.tile_at_end, V.wg_two_tiles);
+    printf("selftest: converting: unrolled loop entered at 64 / 256 threads: %zu / %zu, remainder: %zu / %zu; groups = 4 * 64 - 1: %zu, "
+           "4 * 256 - 1 / + 0 / + 1: %zu / %zu / %zu\n", V.loops.unrolled[0], V.loops.unrolled[1], V.loops.rest[0], V.loops.rest[1],
+           V.loops.end_m1[0], V.loops.end_m1[1], V.loops.end_0[1], V.loops.end_p1[1]);
+    failed += need("a pinned plain table", pinned[0]) + need("a pinned converting table", pinned[1]);
+    failed += need("unit 1", P.unit[0]) + need("unit 2", P.unit[1]) + need("unit 4", P.unit[2]) + need("unit 8", P.unit[3]);
+    failed += need("a vector piece with head, body and tail", P.vec_hbt) + need("a piece that is not a vector piece", P.nonvec);
+    for (const Cover *C : {&P, &V}) {
+        for (int w = 0; w < 4; w++) failed += need("a small piece on each wave", C->small_wave[w]);
+        failed += need("a piece of the workgroup", C->big) + need("a tile ending inside an entry", C->tile_inside) +
+                  need("a tile ending at an entry's end", C->tile_at_end) + need("a workgroup with two tiles", C->wg_two_tiles);
+        failed += need("the unrolled loop at 256 threads", C->loops.unrolled[1]) + need("its remainder", C->loops.rest[1]) +
+                  need("the remainder loop at 64 threads", C->loops.rest[0]) + need("a count of 4 * 256 - 1", C->loops.end_m1[1]) +
+                  need("a count of 4 * 256", C->loops.end_0[1]);
+    }
+    // (plain one-wave pieces hold at most 63 vectors: the unrolled loop at 64 threads is the converting mover's alone)
+    failed += need("the unrolled loop at 64 threads", V.loops.unrolled[0]) + need("4 * 64 - 1 groups", V.loops.end_m1[0]) +
+              need("4 * 256 + 1 groups", V.loops.end_p1[1]);
+    for (int k = 0; k < 4; k++) failed += need("every converting class with head and tail", V.cls_ht[k]);
+
+    // ---- the scatter inputs against the mutants of the narrowing ----
+    static const char *names[4] = {"rounding toward zero goes unseen", "ties away from zero go unseen",
+                                   "flushed subnormal results go unseen", "a fused multiply-convert goes unseen"};
+    size_t cases = 0, judged = 0, min_mut[4] = {SIZE_MAX, SIZE_MAX, SIZE_MAX, SIZE_MAX}, plus_zero = 0, upper_half = 0;
+    size_t neg_zero[2][2] = {{0, 0}, {0, 0}}; // [type][alone, in a group]
+    double max_nan = 0, min_finite = 1;
+    for (size_t ti = 0; ti < ctab.size(); ti++) {
+        const Table &T = ctab[ti];
+        const size_t n = T.elems();
+        for (int dt : {(int)kFloat16, (int)kBFloat16})
+            for (float scale : kScales) {
+                cases++;
+                size_t nan = 0, fin = 0, mut[4] = {0, 0, 0, 0};
+                for (size_t g = 0; g < n; g++) {
+                    const float a = cvt_packed(T, dt, scale, g);
+                    const uint16_t w = narrow_ref(a, scale, dt);
+                    const double v = decode16(w, dt);
+                    nan += std::isnan(v);
+                    fin += std::isfinite(v) && v != 0.0;
+                    if (std::isnan(v)) {
+                        upper_half += !is_nan16(narrow_ref(a, scale, dt, kUpperHalf), dt);
+                        continue; // compared by NaN-ness: every mutant gives a NaN here as well
+                    }
+                    for (int m = 0; m < 4; m++) mut[m] += narrow_ref(a, scale, dt, m + 1) != w;
+                    if (scale == 0.0f) continue; // (there every negative a gives -0)
+                    plus_zero += narrow_ref(a, scale, dt, kPlusZero) != w;
+                    if (w == 0x8000) neg_zero[dt == kBFloat16][paths[ti][g] == 2]++;
+                }
+                const double sn = (double)nan / (double)n, sf = (double)fin / (double)n;
+                auto bad = [&](const char *why) {
+                    failed++;
+                    printf("FAIL %s dtype %d scale %.9g: %s\n", T.name.c_str(), dt, scale, why);
+                };
+                if (T.block != kNonFinite) {
+                    if (sn > max_nan) max_nan = sn;
+                    if (nan * 8 > n) bad("more than 1/8 of the expected elements are NaN");
+                }
+                if (n < 257 || scale == 0.0f) continue;
+                if (sf < min_finite) min_finite = sf;
+                if (fin * 2 < n) bad("fewer than half of the expected elements are finite and non-zero");
+                judged++;
+                for (int m = 0; m < 4; m++) {
+                    if (m == 3 && exact_scale(scale)) continue;
+                    if (mut[m] < min_mut[m]) min_mut[m] = mut[m];
+                    if (!mut[m]) bad(names[m]);
+                }
+            }
+    }
+    printf("selftest: %zu converting scatter cases, %zu of >= 257 elements at a scale other than 0\n", cases, judged);
+    printf("selftest: converting: largest NaN share %.4f, smallest finite non-zero share %.4f\n", max_nan, min_finite);
+    printf("selftest: converting: smallest mutant difference (elements): toward zero %zu, ties away %zu, subnormals flushed %zu, "
+           "fused %zu\n", min_mut[0], min_mut[1], min_mut[2], min_mut[3]);
+    printf("selftest: converting: +0 for a zero product seen in %zu elements, an infinity for a NaN in %zu; -0 expected alone / in a "
+           "group: float16 %zu / %zu, bfloat16 %zu / %zu\n", plus_zero, upper_half, neg_zero[0][0], neg_zero[0][1], neg_zero[1][0],
+           neg_zero[1][1]);
+    failed += need("a -0 that a +0 would miss", plus_zero) + need("a NaN whose upper half reads as an infinity", upper_half);
+    for (int t = 0; t < 2; t++)
+        failed += need("-0 in an element that moves alone", neg_zero[t][0]) + need("-0 in an element of a group", neg_zero[t][1]);
+
+    // ---- lds_check: the operand roles in the full tiles and in the ragged rest ----
+    size_t lds = 0, lds_judged = 0, min_swap = SIZE_MAX;
+    for (const LdsCombo &c : lds_combos())
+        for (size_t nv : kLdsVecs) {
+            lds++;
+            if (!lds_order_sensitive(c)) continue;
+            const size_t es = esize(c.dt), n = nv * 16 / es, nfull = nv / kLdsTileVecs * kLdsTileVecs * 16 / es;
+            Bytes x(n * es), y(n * es);
+            lds_fill(x.data(), c.dt, c.op, n, 0, lds_seed(c.dt, c.op, nv));
+            lds_fill(y.data(), c.dt, c.op, n, 1, lds_seed(c.dt, c.op, nv));
+            Bytes want = x, sw = y;
+            if (reduce_local(c.dt, c.op, y.data(), want.data(), n) || reduce_local(c.dt, c.op, x.data(), sw.data(), n)) {
+                printf("FAIL lds dtype %d op %d: the reference refused\n", c.dt, c.op);
+                failed++;
+                continue;
+            }
+            const size_t part[3] = {0, nfull, n};
+            for (int r = 0; r < 2; r++) {
+                if (part[r + 1] - part[r] < 257) continue;
+                lds_judged++;
+                size_t d = 0;
+                for (size_t i = part[r] * es; i < part[r + 1] * es; i++) d += want[i] != sw[i];
+                if (d < min_swap) min_swap = d;
+                if (!d) {
+                    printf("FAIL lds dtype %d op %d, %zu vectors: swapped operands go unseen in the %s\n", c.dt, c.op, nv,
+                           r ? "ragged rest" : "full tiles");
+                    failed++;
+                }
+            }
+        }
+    printf("selftest: %zu lds cases; %zu order-sensitive parts of >= 257 elements, smallest swap difference %zu bytes\n", lds, lds_judged,
+           min_swap);
+    return failed;
+}
+
+} // namespace
+
 static int selftest()
 {
     Stats S;
@@ -155,14 +441,38 @@ static int selftest()
     printf("selftest: smallest mutant difference (elements): toward zero %zu, ties away %zu, subnormals flushed %zu\n",
            S.min_mut[0], S.min_mut[1], S.min_mut[2]);
     printf("selftest: smallest swap difference %zu bytes (FTAR_2INT: largest %zu)\n", S.min_swap, S.max_swap_2int);
+    S.failed += movers_selftest();
     printf("selftest: %d failed\n", S.failed);
     return S.failed ? 1 : 0;
+}
+
+static int narrow(int dt, const char *fin, const char *fout)
+{
+    const Bytes in = read_file(fin);
+    if (!is16(dt) || in.size() % 4) {
+        fprintf(stderr, "ref_check: narrow wants dtype 16 or 17 and a file of float32\n");
+        return 2;
+    }
+    std::vector<uint16_t> out(in.size() / 4);
+    for (size_t i = 0; i < out.size(); i++) {
+        float a;
+        memcpy(&a, &in[4 * i], 4);
+        out[i] = kmov::narrow_ref(a, 1.0f, dt);
+    }
+    FILE *f = fopen(fout, "wb");
+    if (!f || fwrite(out.data(), 2, out.size(), f) != out.size()) {
+        perror(fout);
+        return 2;
+    }
+    fclose(f);
+    return 0;
 }
 
 int main(int argc, char **argv)
 {
     if (argc == 7 && !strcmp(argv[1], "apply")) return apply(atoi(argv[2]), atoi(argv[3]), argv[4], argv[5], argv[6]);
     if (argc == 2 && !strcmp(argv[1], "selftest")) return selftest();
-    fprintf(stderr, "usage: ref_check apply DTYPE OP IN INOUT OUT | ref_check selftest\n");
+    if (argc == 5 && !strcmp(argv[1], "narrow")) return narrow(atoi(argv[2]), argv[3], argv[4]);
+    fprintf(stderr, "usage: ref_check apply DTYPE OP IN INOUT OUT | ref_check selftest | ref_check narrow DTYPE IN OUT\n");
     return 2;
 }

@@ -343,3 +343,46 @@ def test_segment_kernel_on_half_and_pair_types():
     2^20 / 1024 / 128 / 7 workgroups -- against the same reference, every byte outside a
     destination untouched."""
     _run_checker("seg_check", "types")
+
+
+def test_gather_movers_on_their_own():
+    """gather_check: gather_kernel in both directions through launch_gather, with tables and grids
+    chosen by the checker (tests/kernel_gpu/gen_movers.h) -- element sizes 2, 4, 8, 16; user buffers
+    at every multiple of the type's alignment past a 16-byte boundary (2-byte elements at 0 .. 14,
+    8-byte pairs at 4 and 12, the 16-byte pair at 8), congruent to their packed address or not, and
+    2-byte elements against an odd packed address (units of one byte); entries of one element,
+    around one vector, of 1023 / 1024 / 1025 bytes, around 4 * 64 and 4 * 256 vectors, one tile
+    -1 / 0 / +1 element, an entry ending on a tile edge with another behind it, one entry over five
+    tiles, 320 one-element entries in one tile (the deal over the four waves), 1024 entries; user
+    buffers in device memory or in pinned host memory; grids of ntiles, min(7, ntiles) and 1 (the
+    stride loop).  Expected: concatenation, byte for byte, and every other byte of the arena --
+    guards, gaps, the source side -- untouched.  test_kernel_ref.py counts on the CPU that these
+    tables reach every unit, path, threshold and tile-edge exit."""
+    _run_checker("gather_check")
+
+
+def test_converting_movers_on_their_own():
+    """gather_check cvt: gather_cvt_kernel for float16 and bfloat16 in both directions through
+    launch_gather_cvt -- user buffers at every even offset, packed starts giving classes 8, 4, 2
+    (with head and tail) and 1, the same sizes in elements and the same three grids, a pinned
+    table.  Gather: every 16-bit pattern widened, bit for bit against the reference's decode.
+    Scatter at scales 1, 0.5, 1/3, -1, 2^-12, 0 and 3.0000002 against ONE float32 multiplication and
+    ONE conversion by the reference (encode16((double)(float)((double)scale * a))): every widened
+    pattern, every finite pattern's tie with its neighbour -1 / 0 / +1 ulp of float32, products
+    that round in float32 to such a tie, ties in the subnormal range, the overflow edge, -0 and
+    products underflowing to -0 (alone and in packed groups), float32-subnormal products,
+    infinities and NaNs whose upper 16 bits read as an infinity.  Bit for bit, any NaN where a NaN
+    is expected; test_kernel_ref.py shows that a wrong rounding, a fused multiply-convert, a +0 or
+    a truncated NaN would each be seen."""
+    _run_checker("gather_check", "cvt")
+
+
+def test_lds_reduce_on_its_own():
+    """lds_check: reduce_lds_kernel through launch_reduce_lds with the checker's grid -- all nine
+    element types with every op each has, both kinds of store, 1, 63, 64, 255, 256, 257, 1023, 1024,
+    1025 and 4 * 1024 + 65 vectors at grids of ntiles, min(3, ntiles) and 1, so that one workgroup
+    takes several full tiles and ends in the ragged path.  Inputs with NaN, +-0, infinities and
+    pair padding; expected inout = inout op in by the oracle (the four old types) or the plain
+    reference, bit for bit (NaN-ness where a SUM / PROD expectation is a NaN); `in` and the guards
+    around `inout` untouched."""
+    _run_checker("lds_check")

@@ -1,10 +1,13 @@
-"""The plain reference behind tree_check's and seg_check's `types` matrices
-(tests/kernel_gpu/ref_types.h), pinned on the CPU, and the self-test of those matrices' inputs.
+"""The plain reference behind tree_check's and seg_check's `types` matrices, gather_check's
+converting mode and lds_check (tests/kernel_gpu/ref_types.h), pinned on the CPU, and the self-test
+of those matrices' inputs.
 
 tests/kernel_gpu/ref_check is a host program (no HIP call): `apply` runs the reference over
-operand files, `selftest` generates the inputs of every GPU case and asserts that they can tell
-a wrong kernel from a right one (a wrong rounding, flushed subnormals, swapped operands; the
-conditions are listed in ref_check.cpp).  Both also run in a build with ASan + UBSan.
+operand files, `narrow` its float32 -> 16-bit conversion, `selftest` generates the inputs of every
+GPU case and asserts that they can tell a wrong kernel from a right one (a wrong rounding, flushed
+subnormals, swapped operands, a fused multiply-convert) and that the movers' tables reach what
+they are built to reach (the conditions are listed in ref_check.cpp).  `apply` and `selftest` also
+run in a build with ASan + UBSan.
 
 References here
 * float16 / bfloat16: torch CPU arithmetic in the element type (test_gpu_half.pair), on every
@@ -108,8 +111,48 @@ def test_reference_matches_the_header_rule_on_pairs(ref_check, name):
             assert bad.size == 0, (name, op, bad[:8], x[bad[:8]], y[bad[:8]])
 
 
+@pytest.mark.parametrize("name", ["f16", "bf16"])
+def test_narrowing_reference_matches_numpy(ref_check, name):
+    """`ref_check narrow` (encode16 of a float32: the reference of the converting scatter) against
+    acc32_runner.narrow (numpy's float16 conversion / the bfloat16 bit formula) on every 16-bit
+    pattern widened and moved by 0, 1, half a gap - 1, half a gap and half a gap + 1 ulps of float32
+    either way: the values themselves, their neighbours, and every tie with its two sides.  Bit for
+    bit, a NaN where numpy has one."""
+    import acc32_runner as A
+    dt = DTYPE[name]
+    pat = np.arange(1 << 16, dtype=np.uint16)
+    wide = A.widen(pat, dt).view(np.uint32).astype(np.int64)
+    half = 1 << (23 - (10 if name == "f16" else 7) - 1)  # half the gap of two neighbours, in float32 ulps (normal range)
+    steps = [0, 1, half - 1, half, half + 1]
+    moved = np.concatenate([wide + s for s in steps] + [wide - s for s in steps[1:]])
+    moved = moved[(moved >= 0) & (moved < 1 << 32)].astype(np.uint32)
+    if name == "f16":  # float16's subnormals and the range below them: the gap there is 2^-24 whatever the exponent
+        tiny = np.arange(1 << 11, dtype=np.float64) * 2.0 ** -25  # every subnormal, every tie between two
+        tiny = np.concatenate([tiny, -tiny]).astype(np.float32).view(np.uint32).astype(np.int64)
+        moved = np.concatenate([moved, (tiny[:, None] + np.array([-1, 0, 1])).ravel().clip(0, (1 << 32) - 1).astype(np.uint32)])
+    f = moved.view(np.float32)
+    want = A.narrow(f, dt)
+    with tempfile.TemporaryDirectory(prefix="ftar_ref_") as tmp:
+        fi, fo = os.path.join(tmp, "f32.bin"), os.path.join(tmp, "h16.bin")
+        f.tofile(fi)
+        cp = subprocess.run([ref_check[0], "narrow", str(dt), fi, fo], capture_output=True, text=True, timeout=300)
+        assert cp.returncode == 0, cp.stdout + cp.stderr[-3000:]
+        got = np.fromfile(fo, dtype=np.uint16)
+    assert got.shape == want.shape
+    nan_w, nan_g = np.isnan(A.widen(want, dt)), np.isnan(A.widen(got, dt))
+    assert np.array_equal(nan_w, np.isnan(f)) and np.array_equal(nan_w, nan_g)
+    bad = np.flatnonzero((got != want) & ~nan_w)
+    assert bad.size == 0, (name, bad[:8], moved[bad[:8]], got[bad[:8]], want[bad[:8]])
+
+
 def test_inputs_tell_a_wrong_kernel_from_a_right_one(ref_check):
-    """ref_check selftest: the conditions on the inputs of every case of the GPU matrices."""
+    """ref_check selftest: the conditions on the inputs of every case of the GPU matrices -- the
+    tree and segment checkers' (wrong roundings, swapped operands), and those of gather_check and
+    lds_check: the movers' tables replayed with the product's host functions and every unit, path,
+    threshold, tile-edge exit and converting class counted non-zero; every converting scatter case
+    telling a wrong rounding, flushed subnormals and a fused multiply-convert from the contract;
+    -0 and half-infinity NaNs present; the NaN and finite shares; the LDS reduce's operand roles
+    visible in the full tiles and in the ragged rest."""
     cp = subprocess.run([ref_check[0], "selftest"], capture_output=True, text=True, timeout=600)
     assert cp.returncode == 0, cp.stdout[-3000:] + cp.stderr[-3000:]
     assert cp.stdout.rstrip().endswith("selftest: 0 failed"), cp.stdout[-3000:]
@@ -118,7 +161,8 @@ def test_inputs_tell_a_wrong_kernel_from_a_right_one(ref_check):
 
 def test_reference_under_sanitizers(ref_check):
     """The same program built with ASan + UBSan: the reference over operands that reach every
-    branch of the rounding (specials against every pattern), and the whole self-test."""
+    branch of the rounding (specials against every pattern), and the whole self-test -- the movers'
+    table generators, layouts and replay (gen_movers.h) included."""
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1")
     pat = np.arange(1 << 16, dtype=np.uint16)
     with tempfile.TemporaryDirectory(prefix="ftar_ref_") as tmp:
