@@ -24,6 +24,9 @@ INT32, FLOAT32, INT64, FLOAT64 = 0, 1, 2, 3
 FLOAT16, BFLOAT16 = 16, 17  # 2-byte floats: SUM / PROD / MAX / MIN, rounded in their own format at every combination
 # MPI's pair types (value, index) for MAXLOC / MINLOC; torch has no such dtype: pack_pairs / unpack_pairs
 FLOAT_INT, TWO_INT, DOUBLE_INT = 32, 33, 34
+# the 8- and 16-bit integers and the unsigned ones: all ten ops; SUM / PROD wrap modulo 2^w, MAX / MIN compare in
+# the type's own signedness, the logical ops give 0 / 1
+INT8, UINT8, INT16, UINT16, UINT32, UINT64 = 48, 49, 50, 51, 52, 53
 SUM, PROD, MAX, MIN = 0, 1, 2, 3
 MAXLOC, MINLOC = 16, 17  # the pair types' only ops: the winning (value, index) copied whole, ties to the lower index
 LAND, BAND, LOR, BOR, LXOR, BXOR = 4, 5, 6, 7, 8, 9  # MPI logical / bitwise ops (integer types)
@@ -140,7 +143,13 @@ def lib():
 def _dtype_of(t) -> int:
     import torch
     m = {torch.int32: INT32, torch.float32: FLOAT32, torch.int64: INT64, torch.float64: FLOAT64,
-         torch.float16: FLOAT16, torch.bfloat16: BFLOAT16}
+         torch.float16: FLOAT16, torch.bfloat16: BFLOAT16,
+         torch.int8: INT8, torch.uint8: UINT8}
+    # torch.int16 is NOT mapped: it is the storage view callers use for raw float16 / bfloat16 bits, and the
+    # binding has always refused it rather than guess; an int16 buffer names its type (dtype=INT16)
+    for name, code in (("uint16", UINT16), ("uint32", UINT32), ("uint64", UINT64)):
+        if hasattr(torch, name):  # the unsigned types above 8 bits: newer torch only
+            m[getattr(torch, name)] = code
     if t.dtype not in m:
         raise FtarError(f"unsupported dtype {t.dtype}")
     return m[t.dtype]

@@ -41,6 +41,12 @@ size_t ftar_esize(int dtype)
     case FTAR_FLOAT_INT:
     case FTAR_2INT: return (fdev_has_dtype && fdev_has_dtype(dtype)) ? 8 : 0;
     case FTAR_DOUBLE_INT: return (fdev_has_dtype && fdev_has_dtype(dtype)) ? 16 : 0;
+    case FTAR_INT8:
+    case FTAR_UINT8: return (fdev_has_dtype && fdev_has_dtype(dtype)) ? 1 : 0;
+    case FTAR_INT16:
+    case FTAR_UINT16: return (fdev_has_dtype && fdev_has_dtype(dtype)) ? 2 : 0;
+    case FTAR_UINT32: return (fdev_has_dtype && fdev_has_dtype(dtype)) ? 4 : 0;
+    case FTAR_UINT64: return (fdev_has_dtype && fdev_has_dtype(dtype)) ? 8 : 0;
     default: return 0;
     }
 }
@@ -411,13 +417,16 @@ static void xcache_forget(ftar_comm *c, uint64_t id)
         if (c->xcache[k].id == id) c->xcache[k].id = 0;
 }
 
-/* `bytes` moved as whole elements of the widest type that divides them: int32, or a 2-byte
- * type where a 2-byte vector has an odd count (bytes / 4 int32 elements dropped its last one) */
+/* `bytes` moved as whole elements of the widest type (4, 2 or 1 bytes) that divides them AND that
+ * both addresses are aligned to: int32, a 2-byte type where a 2-byte vector has an odd count
+ * (bytes / 4 int32 elements dropped its last one), a 1-byte type where a 1-byte vector has an odd
+ * count or starts at an odd address (its scalar head and tail would be misaligned wider accesses) */
 static fdev_seg copy_bytes_seg(void *dst, const void *src, size_t bytes, int *dtype)
 {
-    const size_t es = bytes % 4 ? 2 : 4;
+    const size_t low = bytes | (size_t)(uintptr_t)dst | (size_t)(uintptr_t)src;
+    const size_t es = low & 1 ? 1 : low & 2 ? 2 : 4;
     fdev_seg s = {FDEV_COPY, 0, dst, src, NULL, bytes / es, NULL};
-    *dtype = es == 2 ? FTAR_FLOAT16 : FTAR_INT32;
+    *dtype = es == 1 ? FTAR_UINT8 : es == 2 ? FTAR_FLOAT16 : FTAR_INT32;
     return s;
 }
 

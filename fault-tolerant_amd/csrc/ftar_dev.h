@@ -100,7 +100,7 @@ int fdev_run(ftar_dev *d, int dtype, int op, const fdev_seg *segs, int nseg, int
  * FDEV_MAX_GATHER) entries of `table` into the dense vector `packed` (scatter = 0: packed[off ..
  * off + bytes) = ptr[0 .. bytes)), or scatters them back out of it (scatter = 1).  The entries
  * are non-empty, ascending and dense in packed space (table[0].off = 0, table[i + 1].off =
- * table[i].off + table[i].bytes), offsets and sizes multiples of `esize` (2, 4, 8, 16).  The
+ * table[i].off + table[i].bytes), offsets and sizes multiples of `esize` (1, 2, 4, 8, 16).  The
  * table is copied: the caller's may go out of scope at once.  Weak: a device layer that does
  * not define it (the host-sim test layer) leaves the shared host C to move the entries with
  * fdev_run's FDEV_COPY segments. */
@@ -249,8 +249,8 @@ int fdev_set_reduce_variant(int v);
 
 /* 1 if the device layer has kernels for element type `dtype`.  Weak: a device layer that
  * does not define it (the host-sim test layer) has the four original types only, and the
- * shared host C then refuses the 2-byte float types and the pair types at the boundary
- * (ftar_esize). */
+ * shared host C then refuses the 2-byte float types, the pair types and the 8-, 16-bit and
+ * unsigned integer types at the boundary (ftar_esize). */
 int fdev_has_dtype(int dtype) __attribute__((weak));
 
 const char *fdev_last_error(void);

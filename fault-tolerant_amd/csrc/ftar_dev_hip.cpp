@@ -68,11 +68,17 @@ int set_err(hipError_t e, const char *what)
 size_t esize_of(int dtype)
 {
     switch (dtype) {
+    case ftar::kInt8:
+    case ftar::kUInt8: return 1;
     case ftar::kFloat16:
-    case ftar::kBFloat16: return 2;
+    case ftar::kBFloat16:
+    case ftar::kInt16:
+    case ftar::kUInt16: return 2;
     case ftar::kInt32:
+    case ftar::kUInt32:
     case ftar::kFloat32: return 4;
     case ftar::kInt64:
+    case ftar::kUInt64:
     case ftar::kFloat64:
     case ftar::kFloatInt:
     case ftar::k2Int: return 8;

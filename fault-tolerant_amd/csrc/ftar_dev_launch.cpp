@@ -316,7 +316,7 @@ static int gather_launch(ftar_dev *d, void *packed, const fdev_gent *table, int 
                          int scatter, int tag)
 {
     if (!packed || !table || n < 1 || n > ftar::kMaxGather || tag < 0 || tag >= FDEV_NTAGS ||
-        !(esize == 2 || esize == 4 || esize == 8 || esize == 16)) {
+        !(esize == 1 || esize == 2 || esize == 4 || esize == 8 || esize == 16)) {
         snprintf(g_err, sizeof(g_err), "fdev_gather: bad arguments");
         return 13;
     }

@@ -8,7 +8,8 @@ namespace ftar {
 
 enum {
     kInt32 = 0, kFloat32 = 1, kInt64 = 2, kFloat64 = 3, kFloat16 = 16, kBFloat16 = 17,
-    kFloatInt = 32, k2Int = 33, kDoubleInt = 34 // MPI's pair types: 8, 8 and 16 bytes, kMaxloc / kMinloc only
+    kFloatInt = 32, k2Int = 33, kDoubleInt = 34, // MPI's pair types: 8, 8 and 16 bytes, kMaxloc / kMinloc only
+    kInt8 = 48, kUInt8 = 49, kInt16 = 50, kUInt16 = 51, kUInt32 = 52, kUInt64 = 53 // ops 0..9 (canon_dtype)
 };
 enum {
     kSum = 0, kProd = 1, kMax = 2, kMin = 3, kLand = 4, kBand = 5, kLor = 6, kBor = 7, kLxor = 8, kBxor = 9,
@@ -17,6 +18,23 @@ enum {
 constexpr int kNumOps = 10; // logical / bitwise ops (>= kLand) exist for the integer types only
 // an op some element type has (which types: with_op in ftar_kernels.hip)
 inline bool op_known(int op) { return (op >= 0 && op < kNumOps) || op == kMaxloc || op == kMinloc; }
+// The canonical dispatch: the element type whose instantiation computes `op` on `dtype`.  Within
+// one width, signed and unsigned integers give identical bits for SUM and PROD (modulo 2^w) and
+// for the logical and bitwise ops; only MAX / MIN compare.  So each width has ONE type with all
+// ten ops (uint8_t, uint16_t, int32_t, int64_t) and its sibling is instantiated for MAX / MIN
+// alone.  Every dtype dispatcher of ftar_kernels.hip switches on this.  Never across widths: the
+// planners derive heads, tails and vector counts from the element size.
+inline int canon_dtype(int dtype, int op)
+{
+    const bool order = op == kMax || op == kMin;
+    switch (dtype) {
+    case kInt8: return order ? kInt8 : kUInt8;
+    case kInt16: return order ? kInt16 : kUInt16;
+    case kUInt32: return order ? kUInt32 : kInt32;
+    case kUInt64: return order ? kUInt64 : kInt64;
+    default: return dtype;
+    }
+}
 enum { kCopy = 0, kReduce = 1 };
 
 constexpr int kMaxKSegs = 48; // 16 user segments x (head, body, tail); 2.3 KB of kernarg
@@ -218,7 +236,7 @@ struct GatherArgs {
     char *packed;
     const GEntry *tab; // device memory
     int n;
-    unsigned es;       // element size of the call: 2, 4, 8, 16
+    unsigned es;       // element size of the call: 1, 2, 4, 8, 16
     size_t total;      // bytes of the packed vector
     unsigned ntiles;
     KSignal sig;       // optional completion signal

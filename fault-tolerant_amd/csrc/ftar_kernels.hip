@@ -38,6 +38,21 @@ namespace ftar {
 template <typename T> struct Arith { using U = T; };
 template <> struct Arith<int32_t> { using U = uint32_t; };
 template <> struct Arith<int64_t> { using U = uint64_t; };
+// The 8- and 16-bit integers: C promotes both operands to (signed) int, and 65535 * 65535
+// overflows it -- undefined.  SUM / PROD are done in uint32_t and truncated: modulo 2^w.
+template <> struct Arith<uint8_t> { using U = uint32_t; };
+template <> struct Arith<int8_t> { using U = uint32_t; };
+template <> struct Arith<uint16_t> { using U = uint32_t; };
+template <> struct Arith<int16_t> { using U = uint32_t; };
+
+// Element types instantiated for MAX / MIN only: within one width signed and unsigned give the
+// same bits for every other op, which runs on the width's canonical type (canon_dtype,
+// ftar_kernels.h: uint8_t, uint16_t, int32_t, int64_t).
+template <typename T> struct is_order_only : std::false_type {};
+template <> struct is_order_only<int8_t> : std::true_type {};
+template <> struct is_order_only<int16_t> : std::true_type {};
+template <> struct is_order_only<uint32_t> : std::true_type {};
+template <> struct is_order_only<uint64_t> : std::true_type {};
 
 // The 2-byte float types: plain bit containers (sizeof == 2 gives 8 elements per 16-byte
 // vector); the arithmetic is in the apply / apply16 overloads below.
@@ -142,7 +157,8 @@ FTAR_APPLY_LOC(di_t, kMinloc)
 
 // Runs fn(std::integral_constant<int, OP>) for the runtime op: one instantiation per op
 // the element type has (the logical / bitwise ops only for the integer types, MAXLOC /
-// MINLOC and nothing else for the pair types).
+// MINLOC and nothing else for the pair types, MAX / MIN and nothing else for the order-only
+// integer types).
 template <typename T, typename Fn>
 static hipError_t with_op(int op, Fn &&fn)
 {
@@ -151,6 +167,12 @@ static hipError_t with_op(int op, Fn &&fn)
         switch (op) {
         case kMaxloc: return fn(integral_constant<int, kMaxloc>{});
         case kMinloc: return fn(integral_constant<int, kMinloc>{});
+        default: return hipErrorInvalidValue;
+        }
+    } else if constexpr (is_order_only<T>::value) {
+        switch (op) {
+        case kMax: return fn(integral_constant<int, kMax>{});
+        case kMin: return fn(integral_constant<int, kMin>{});
         default: return hipErrorInvalidValue;
         }
     } else {
@@ -176,9 +198,95 @@ static hipError_t with_op(int op, Fn &&fn)
     }
 }
 
+// The 8- and 16-bit integers' vector path, one 32-bit register (two or four elements) at a time.
+// gfx950 has packed 16-bit integer add, mul_lo, max, min and shifts (v_pk_*_u16 / _i16, reached
+// through ext_vector_type arithmetic and the elementwise builtins) and no packed 8-bit ALU at all:
+// the generic per-element loop unpacks every byte (v_bfe / v_lshrrev), combines it and packs the
+// results again (v_perm / v_lshl_or).  The forms below are the same functions of the bits:
+//   bitwise ops        whole-register logic, whatever the width;
+//   logical ops        per element "any bit set" as 0 / 1 -- 16-bit: min(x, 1) unsigned; 8-bit:
+//                      SWAR, bit 7 of (low 7 bits + 0x7f) | x moved down -- then and / or / xor
+//                      (LOR: one "any bit set" of x | y);
+//   16-bit arithmetic  the packed ops themselves (unsigned vector arithmetic wraps: no promotion
+//                      to int takes place on vector operands);
+//   8-bit SUM          carry-isolating SWAR: the low 7 bits of every byte added with bit 7 clear
+//                      (no carry leaves a byte), bit 7 put back as the xor of the operands' and
+//                      the carry into it;
+//   8-bit PROD         even and odd bytes through the packed 16-bit multiply.  The low byte of a
+//                      product depends on the operands' low bytes only (even bytes: a as loaded);
+//                      (a_odd << 8) * b_odd is the product's low byte in the odd position already;
+//                      one v_perm_b32 takes the even bytes of the one and the odd bytes of the other;
+//   8-bit MAX / MIN    even and odd bytes through the packed 16-bit max / min with the byte in
+//                      the HIGH half of its 16-bit lane, where the lane's own signedness is the
+//                      byte's.  Odd bytes: the operands as loaded -- a 16-bit lane orders by its
+//                      high byte first, so the high byte of the lane's max IS the max of the high
+//                      bytes, whatever the low bytes did.  Even bytes: shifted up by 8.  One
+//                      v_perm_b32 puts the four high bytes in place.  An integer max is one of its
+//                      operands, so this is (x > y) ? x : y bit for bit.
+typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
+typedef short ss2_t __attribute__((ext_vector_type(2)));
+template <typename T> struct is_narrow_int : std::integral_constant<bool, std::is_integral<T>::value && sizeof(T) <= 2> {};
+
+template <int OP, typename V>
+__device__ __forceinline__ uint32_t pk_order16(uint32_t a, uint32_t b)
+{
+    const V x = __builtin_bit_cast(V, a), y = __builtin_bit_cast(V, b);
+    return __builtin_bit_cast(uint32_t, OP == kMax ? __builtin_elementwise_max(x, y) : __builtin_elementwise_min(x, y));
+}
+__device__ __forceinline__ uint32_t pk_mul16(uint32_t a, uint32_t b)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2_t, a) * __builtin_bit_cast(us2_t, b));
+}
+__device__ __forceinline__ uint32_t pk_shl16(uint32_t a, int k)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2_t, a) << (us2_t)(unsigned short)k);
+}
+__device__ __forceinline__ uint32_t pk_shr16(uint32_t a, int k)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2_t, a) >> (us2_t)(unsigned short)k);
+}
+// per element 1 where any bit is set, else 0
+__device__ __forceinline__ uint32_t nz16(uint32_t a) { return pk_order16<kMin, us2_t>(a, 0x00010001u); }
+__device__ __forceinline__ uint32_t nz8(uint32_t a)
+{
+    return ((((a & 0x7f7f7f7fu) + 0x7f7f7f7fu) | a) >> 7) & 0x01010101u;
+}
+
+template <typename T, int OP>
+__device__ __forceinline__ uint32_t pk_int(uint32_t a, uint32_t b)
+{
+    constexpr bool k8 = sizeof(T) == 1;
+    constexpr uint32_t kEven = 0x00ff00ffu, kOdd = 0xff00ff00u;
+    // v_perm_b32 selectors (byte i of the result: 0..3 = byte of the second source, 4..7 = of the first)
+    constexpr uint32_t kOddOfFirstEvenOfSecond = 0x07020500u; // {first.3, second.2, first.1, second.0}
+    constexpr uint32_t kHighBytesInterleaved = 0x07030501u;   // {first.3, second.3, first.1, second.1}
+    if constexpr (OP == kBand) return a & b;
+    else if constexpr (OP == kBor) return a | b;
+    else if constexpr (OP == kBxor) return a ^ b;
+    else if constexpr (OP == kLand) return k8 ? nz8(a) & nz8(b) : nz16(a) & nz16(b);
+    else if constexpr (OP == kLor) return k8 ? nz8(a | b) : nz16(a | b);
+    else if constexpr (OP == kLxor) return k8 ? nz8(a) ^ nz8(b) : nz16(a) ^ nz16(b);
+    else if constexpr (OP == kSum) {
+        if constexpr (k8) return ((a & 0x7f7f7f7fu) + (b & 0x7f7f7f7fu)) ^ ((a ^ b) & 0x80808080u);
+        else return __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2_t, a) + __builtin_bit_cast(us2_t, b));
+    } else if constexpr (OP == kProd) {
+        if constexpr (k8)
+            return __builtin_amdgcn_perm(pk_mul16(a & kOdd, pk_shr16(b, 8)), pk_mul16(a, b & kEven), kOddOfFirstEvenOfSecond);
+        else return pk_mul16(a, b);
+    } else { // MAX / MIN in the type's own signedness
+        using V = typename std::conditional<std::is_signed<T>::value, ss2_t, us2_t>::type;
+        if constexpr (k8)
+            return __builtin_amdgcn_perm(pk_order16<OP, V>(a, b), pk_order16<OP, V>(pk_shl16(a, 8), pk_shl16(b, 8)),
+                                         kHighBytesInterleaved);
+        else return pk_order16<OP, V>(a, b);
+    }
+}
+
 template <typename T, int OP>
 __device__ __forceinline__ uint4 apply16(uint4 a, uint4 b)
 {
+    if constexpr (is_narrow_int<T>::value)
+        return make_uint4(pk_int<T, OP>(a.x, b.x), pk_int<T, OP>(a.y, b.y), pk_int<T, OP>(a.z, b.z), pk_int<T, OP>(a.w, b.w));
     constexpr int E = 16 / sizeof(T);
     T xa[E], xb[E];
     __builtin_memcpy(xa, &a, 16);
@@ -347,6 +455,7 @@ __device__ __forceinline__ bool stage_copy_vec(const KSignal &G)
         for (size_t i = done + threadIdx.x; i < G.stage_n; i += blockDim.x) {
             if (G.stage_es == 8) ((unsigned long long *)G.stage_dst)[i] = ((const unsigned long long *)G.stage_src)[i];
             else if (G.stage_es == 2) ((unsigned short *)G.stage_dst)[i] = ((const unsigned short *)G.stage_src)[i];
+            else if (G.stage_es == 1) ((unsigned char *)G.stage_dst)[i] = ((const unsigned char *)G.stage_src)[i];
             else ((unsigned *)G.stage_dst)[i] = ((const unsigned *)G.stage_src)[i];
         }
     return true;
@@ -359,6 +468,7 @@ __device__ __forceinline__ void signal_stage(const KSignal &G)
     } else if (G.stage_es == 16) stage_copy<unsigned long long>(G, 2 * G.stage_n); // 8-byte aligned: two halves
     else if (G.stage_es == 8) stage_copy<unsigned long long>(G, G.stage_n);
     else if (G.stage_es == 2) stage_copy<unsigned short>(G, G.stage_n);
+    else if (G.stage_es == 1) stage_copy<unsigned char>(G, G.stage_n);
     else stage_copy<unsigned>(G, G.stage_n);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -714,7 +824,7 @@ static hipError_t launch_tree_t(int op, int p, const TreeArgs &A, unsigned grid,
 
 hipError_t launch_tree(int dtype, int op, int p, const TreeArgs &A, unsigned grid, hipStream_t s)
 {
-    switch (dtype) {
+    switch (canon_dtype(dtype, op)) {
     case kInt32: return launch_tree_t<int32_t>(op, p, A, grid, s);
     case kFloat32: return launch_tree_t<float>(op, p, A, grid, s);
     case kInt64: return launch_tree_t<int64_t>(op, p, A, grid, s);
@@ -724,6 +834,12 @@ hipError_t launch_tree(int dtype, int op, int p, const TreeArgs &A, unsigned gri
     case kFloatInt: return launch_tree_t<fi_t>(op, p, A, grid, s);
     case k2Int: return launch_tree_t<ii_t>(op, p, A, grid, s);
     case kDoubleInt: return launch_tree_t<di_t>(op, p, A, grid, s);
+    case kInt8: return launch_tree_t<int8_t>(op, p, A, grid, s);
+    case kUInt8: return launch_tree_t<uint8_t>(op, p, A, grid, s);
+    case kInt16: return launch_tree_t<int16_t>(op, p, A, grid, s);
+    case kUInt16: return launch_tree_t<uint16_t>(op, p, A, grid, s);
+    case kUInt32: return launch_tree_t<uint32_t>(op, p, A, grid, s);
+    case kUInt64: return launch_tree_t<uint64_t>(op, p, A, grid, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -790,7 +906,7 @@ static hipError_t launch_batch_t(int op, int p, const TreeBatch &B, unsigned gri
 
 hipError_t launch_tree_batch(int dtype, int op, int p, const TreeBatch &B, unsigned grid, hipStream_t s)
 {
-    switch (dtype) {
+    switch (canon_dtype(dtype, op)) {
     case kInt32: return launch_batch_t<int32_t>(op, p, B, grid, s);
     case kFloat32: return launch_batch_t<float>(op, p, B, grid, s);
     case kInt64: return launch_batch_t<int64_t>(op, p, B, grid, s);
@@ -800,6 +916,12 @@ hipError_t launch_tree_batch(int dtype, int op, int p, const TreeBatch &B, unsig
     case kFloatInt: return launch_batch_t<fi_t>(op, p, B, grid, s);
     case k2Int: return launch_batch_t<ii_t>(op, p, B, grid, s);
     case kDoubleInt: return launch_batch_t<di_t>(op, p, B, grid, s);
+    case kInt8: return launch_batch_t<int8_t>(op, p, B, grid, s);
+    case kUInt8: return launch_batch_t<uint8_t>(op, p, B, grid, s);
+    case kInt16: return launch_batch_t<int16_t>(op, p, B, grid, s);
+    case kUInt16: return launch_batch_t<uint16_t>(op, p, B, grid, s);
+    case kUInt32: return launch_batch_t<uint32_t>(op, p, B, grid, s);
+    case kUInt64: return launch_batch_t<uint64_t>(op, p, B, grid, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -1135,7 +1257,7 @@ hipError_t launch_gather_cvt(const GatherArgs &A, int dtype, float scale, int sc
 
 hipError_t launch_segments(int dtype, int op, const KSegList &L, unsigned grid, hipStream_t s)
 {
-    switch (dtype) {
+    switch (canon_dtype(dtype, op)) {
     case kInt32: return launch_t<int32_t>(op, L, grid, s);
     case kFloat32: return launch_t<float>(op, L, grid, s);
     case kInt64: return launch_t<int64_t>(op, L, grid, s);
@@ -1145,6 +1267,12 @@ hipError_t launch_segments(int dtype, int op, const KSegList &L, unsigned grid, 
     case kFloatInt: return launch_t<fi_t>(op, L, grid, s);
     case k2Int: return launch_t<ii_t>(op, L, grid, s);
     case kDoubleInt: return launch_t<di_t>(op, L, grid, s);
+    case kInt8: return launch_t<int8_t>(op, L, grid, s);
+    case kUInt8: return launch_t<uint8_t>(op, L, grid, s);
+    case kInt16: return launch_t<int16_t>(op, L, grid, s);
+    case kUInt16: return launch_t<uint16_t>(op, L, grid, s);
+    case kUInt32: return launch_t<uint32_t>(op, L, grid, s);
+    case kUInt64: return launch_t<uint64_t>(op, L, grid, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -1165,7 +1293,7 @@ hipError_t launch_reduce_lds(int dtype, int op, void *inout, const void *in, siz
 {
     uint4 *io = (uint4 *)inout;
     const uint4 *i = (const uint4 *)in;
-    switch (dtype) {
+    switch (canon_dtype(dtype, op)) {
     case kInt32: return launch_lds_t<int32_t>(op, io, i, nvec, grid, s, nts);
     case kFloat32: return launch_lds_t<float>(op, io, i, nvec, grid, s, nts);
     case kInt64: return launch_lds_t<int64_t>(op, io, i, nvec, grid, s, nts);
@@ -1175,6 +1303,12 @@ hipError_t launch_reduce_lds(int dtype, int op, void *inout, const void *in, siz
     case kFloatInt: return launch_lds_t<fi_t>(op, io, i, nvec, grid, s, nts);
     case k2Int: return launch_lds_t<ii_t>(op, io, i, nvec, grid, s, nts);
     case kDoubleInt: return launch_lds_t<di_t>(op, io, i, nvec, grid, s, nts);
+    case kInt8: return launch_lds_t<int8_t>(op, io, i, nvec, grid, s, nts);
+    case kUInt8: return launch_lds_t<uint8_t>(op, io, i, nvec, grid, s, nts);
+    case kInt16: return launch_lds_t<int16_t>(op, io, i, nvec, grid, s, nts);
+    case kUInt16: return launch_lds_t<uint16_t>(op, io, i, nvec, grid, s, nts);
+    case kUInt32: return launch_lds_t<uint32_t>(op, io, i, nvec, grid, s, nts);
+    case kUInt64: return launch_lds_t<uint64_t>(op, io, i, nvec, grid, s, nts);
     default: return hipErrorInvalidValue;
     }
 }

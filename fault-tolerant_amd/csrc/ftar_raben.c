@@ -624,7 +624,8 @@ int ftar_allreduce_rabenseifner_host(const void *sbuf, void *rbuf, size_t count,
      * SUM/PROD -- but not float MAX/MIN (NaN, signed zeros), which stay one call. */
     int p = c->size;
     int nchunk = 1;
-    int commutes = dtype == FTAR_INT32 || dtype == FTAR_INT64 || op == FTAR_SUM || op == FTAR_PROD;
+    int commutes = dtype == FTAR_INT32 || dtype == FTAR_INT64 || (dtype >= FTAR_INT8 && dtype <= FTAR_UINT64) ||
+                   op == FTAR_SUM || op == FTAR_PROD; /* every integer type, every op it has */
     if (c->host_pipe && commutes && c->redundancy != 1 && c->loop_seconds <= 0 && p >= 2 && (p & (p - 1)) == 0 &&
         bytes >= HOST_PIPE_MIN) {
         nchunk = (int)(bytes / HOST_PIPE_CHUNK);
@@ -643,7 +644,7 @@ int ftar_allreduce_rabenseifner_host(const void *sbuf, void *rbuf, size_t count,
         return FTAR_SUCCESS;
     }
     size_t per = (count + (size_t)nchunk - 1) / (size_t)nchunk;
-    per = (per + 63) / 64 * 64; /* chunk boundaries on 256-byte multiples */
+    per = (per + 63) / 64 * 64; /* chunk boundaries on multiples of 64 elements: 256 bytes at 4, 64 at 1 (16-byte multiples at every size) */
     int n = 0;
     for (size_t off = 0; off < count; off += per, n++) {
         size_t m = count - off < per ? count - off : per;

@@ -32,8 +32,12 @@
 #include <stdio.h>
 #include <string.h>
 
+/* Both counts are in elements.  What is relied on is that they are multiples of 16 BYTES at every
+ * element size, so that a stripe and its relay slot stay co-aligned with the window for the
+ * 16-byte vector bodies: at the smallest element, 1 byte, they are 256 and 64 bytes. */
 #define STRIPE_ALIGN 256 /* elements; interior stripe boundaries are multiples of this */
 #define SLOT_PAD 64      /* elements; a relay slot keeps its source's offset modulo this */
+_Static_assert(STRIPE_ALIGN % 16 == 0 && SLOT_PAD % 16 == 0, "16-byte multiples at 1-byte elements");
 #define MAX_RELAY_RECEIVERS 8
 
 void ftar_plan_clear(ftar_plan *p) { memset(p->npull, 0, sizeof(p->npull)); }

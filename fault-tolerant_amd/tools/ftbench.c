@@ -87,11 +87,13 @@ static int run16(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm
                  int multi, int acc32);
 /* the pair-type job (MAXLOC) */
 static int runpair(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev);
+/* the job on the 8-, 16-bit and unsigned integers (SUM, checked modulo 2^w) */
+static int runint(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev);
 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: ftbench <raben|rd> <count> <calls> [f32|f16|bf16|float_int|2int|double_int]\n");
+        fprintf(stderr, "usage: ftbench <raben|rd> <count> <calls> [f32|f16|bf16|float_int|2int|double_int|i8|u8|i16|u16|u32|u64]\n");
         return 2;
     }
     int rd = !strcmp(argv[1], "rd");
@@ -99,15 +101,22 @@ int main(int argc, char **argv)
     int calls = atoi(argv[3]);
     if (count == 0 || calls < 1 || calls > MAX_CALLS) return 2;
     const char *tn = argc > 4 ? argv[4] : getenv("FTBENCH_DTYPE");
-    int dt16 = 0, dtpair = 0;
+    int dt16 = 0, dtpair = 0, dtint = -1;
     if (tn && *tn && strcmp(tn, "f32")) {
         if (!strcmp(tn, "f16")) dt16 = FTAR_FLOAT16;
         else if (!strcmp(tn, "bf16")) dt16 = FTAR_BFLOAT16;
         else if (!strcmp(tn, "float_int")) dtpair = FTAR_FLOAT_INT;
         else if (!strcmp(tn, "2int")) dtpair = FTAR_2INT;
         else if (!strcmp(tn, "double_int")) dtpair = FTAR_DOUBLE_INT;
+        else if (!strcmp(tn, "i8")) dtint = FTAR_INT8;
+        else if (!strcmp(tn, "u8")) dtint = FTAR_UINT8;
+        else if (!strcmp(tn, "i16")) dtint = FTAR_INT16;
+        else if (!strcmp(tn, "u16")) dtint = FTAR_UINT16;
+        else if (!strcmp(tn, "u32")) dtint = FTAR_UINT32;
+        else if (!strcmp(tn, "u64")) dtint = FTAR_UINT64;
         else {
-            fprintf(stderr, "ftbench: element type %s is not f32, f16, bf16, float_int, 2int or double_int\n", tn);
+            fprintf(stderr, "ftbench: element type %s is not f32, f16, bf16, float_int, 2int, double_int, i8, u8, i16, "
+                            "u16, u32 or u64\n", tn);
             return 2;
         }
     }
@@ -121,7 +130,7 @@ int main(int argc, char **argv)
     CHECK_HIP(hipSetDevice(dev));
     const char *me = getenv("FTBENCH_MULTI");
     const int multi = me && *me ? atoi(me) : 0;
-    if (me && *me && (multi < 1 || multi > FTAR_MULTI_MAX || (size_t)multi > count || dtpair)) {
+    if (me && *me && (multi < 1 || multi > FTAR_MULTI_MAX || (size_t)multi > count || dtpair || dtint >= 0)) {
         fprintf(stderr, "ftbench: FTBENCH_MULTI=%s: 1 .. min(count, %d) buffers of f32, f16 or bf16\n", me,
                 FTAR_MULTI_MAX);
         return 2;
@@ -134,6 +143,7 @@ int main(int argc, char **argv)
     }
     if (dt16) return run16(rd, count, calls, (ftar_dtype)dt16, comm, wrank, wsize, dev, multi, acc32);
     if (dtpair) return runpair(rd, count, calls, (ftar_dtype)dtpair, comm, wrank, wsize, dev);
+    if (dtint >= 0) return runint(rd, count, calls, (ftar_dtype)dtint, comm, wrank, wsize, dev);
 
     /* FTBENCH_PATTERN=1: x_r[i] = (7 i + 13 r) mod 4096 instead of r, so every element
      * has its own exact sum (all partial sums are integers < 2^24) and a misplaced
@@ -385,6 +395,71 @@ static int runpair(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *co
                "\"uniform\": %s, \"hbm_bytes\": %.0f}",
                c ? ", " : "", rc[c], ms[c], rec[c], size_after[c], value[c], index[c], uniform[c] ? "true" : "false",
                hbm[c]);
+    printf("]}\n");
+    fflush(stdout);
+    ftar_finalize(comm);
+    (void)hipFree(s);
+    (void)hipFree(r);
+    free(h);
+    return 0;
+}
+
+/* rank q's contribution to element i: a small value, so the exact sum is known; it is compared
+ * modulo 2^w (at 64 ranks the 8-bit sum of the plain job, 2016, wraps) */
+static uint64_t int_value(int pattern, size_t i, int q) { return pattern ? (7 * i + 13 * (size_t)q) % 4 : (uint64_t)q; }
+
+static int runint(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev)
+{
+    const char *pe = getenv("FTBENCH_PATTERN");
+    const int pattern = pe && atoi(pe) != 0;
+    const size_t es = dt == FTAR_INT8 || dt == FTAR_UINT8 ? 1 : dt == FTAR_INT16 || dt == FTAR_UINT16 ? 2 : dt == FTAR_UINT32 ? 4 : 8;
+    const uint64_t mask = es == 8 ? ~0ull : (1ull << (8 * es)) - 1;
+    unsigned char *h = malloc(count * es);
+    if (!h) return 4;
+    for (size_t i = 0; i < count; i++) {
+        const uint64_t v = int_value(pattern, i, wrank); /* little-endian: the low es bytes */
+        memcpy(h + i * es, &v, es);
+    }
+    void *s = NULL, *r = NULL;
+    CHECK_HIP(hipMalloc(&s, count * es));
+    CHECK_HIP(hipMalloc(&r, count * es));
+    CHECK_HIP(hipMemcpy(s, h, count * es, hipMemcpyHostToDevice));
+    CHECK_HIP(hipDeviceSynchronize());
+
+    double ms[MAX_CALLS], value[MAX_CALLS], hbm[MAX_CALLS];
+    int rc[MAX_CALLS], rec[MAX_CALLS], size_after[MAX_CALLS], uniform[MAX_CALLS], step0_copy = 0;
+    for (int c = 0; c < calls; c++) {
+        rc[c] = rd ? ftar_recursive_doubling(s, r, count, dt, FTAR_SUM, comm)
+                   : ftar_allreduce_rabenseifner(s, r, count, dt, FTAR_SUM, comm);
+        ftar_stats st;
+        ftar_last_stats(comm, &st);
+        ms[c] = st.wall_s * 1e3;
+        hbm[c] = st.hbm_bytes;
+        rec[c] = st.recoveries;
+        size_after[c] = st.comm_size_after;
+        step0_copy |= st.step0_copy;
+        CHECK_HIP(hipMemcpy(h, r, count * es, hipMemcpyDeviceToHost));
+        uint64_t first = 0;
+        memcpy(&first, h, es);
+        value[c] = (double)first;
+        uniform[c] = 1;
+        const int members = size_after[c]; /* the original ranks 0 .. members-1 (no fault) */
+        for (size_t i = 0; i < count; i++) {
+            uint64_t sum = 0, got = 0;
+            for (int q = 0; q < members; q++) sum += int_value(pattern, i, q);
+            memcpy(&got, h + i * es, es);
+            if (got != (sum & mask)) {
+                uniform[c] = 0;
+                break;
+            }
+        }
+    }
+    printf("{\"rank\": %d, \"size\": %d, \"device\": %d, \"step0_copy\": %d, \"calls\": [", wrank, wsize, dev,
+           step0_copy);
+    for (int c = 0; c < calls; c++)
+        printf("%s{\"rc\": %d, \"ms\": %.4f, \"recoveries\": %d, \"comm_size\": %d, \"value\": %.1f, \"uniform\": %s, "
+               "\"hbm_bytes\": %.0f}",
+               c ? ", " : "", rc[c], ms[c], rec[c], size_after[c], value[c], uniform[c] ? "true" : "false", hbm[c]);
     printf("]}\n");
     fflush(stdout);
     ftar_finalize(comm);

@@ -50,7 +50,7 @@ typedef enum {
     FTAR_INT64 = 2,
     FTAR_FLOAT64 = 3,
     /* The 2-byte float types (IEEE binary16 and bfloat16).  Every value not listed here, 4..15,
-     * 18..31 and 35.. included, is FTAR_ERR_ARG; like the other float types they have SUM, PROD, MAX
+     * 18..31, 35..47 and 54.. included, is FTAR_ERR_ARG; like the other float types they have SUM, PROD, MAX
      * and MIN only (FTAR_LAND..FTAR_BXOR: FTAR_ERR_OP).
      *   SUM / PROD  one correctly rounded IEEE operation per combination in the element's own
      *               format: round to nearest even, subnormals kept, overflow to +-inf, a NaN
@@ -68,7 +68,27 @@ typedef enum {
      * MAXLOC / MINLOC on any other type).  Buffers need the struct's alignment only (4, 4, 8). */
     FTAR_FLOAT_INT = 32,  /* MPI_FLOAT_INT:  ftar_float_int,  8 bytes */
     FTAR_2INT = 33,       /* MPI_2INT:       ftar_2int,       8 bytes */
-    FTAR_DOUBLE_INT = 34  /* MPI_DOUBLE_INT: ftar_double_int, 16 bytes (LP64 C layout: 4 bytes of padding) */
+    FTAR_DOUBLE_INT = 34, /* MPI_DOUBLE_INT: ftar_double_int, 16 bytes (LP64 C layout: 4 bytes of padding) */
+    /* The 8-bit and 16-bit integers and the unsigned ones: with FTAR_INT32 / FTAR_INT64 every
+     * fixed-width integer type MPI has.  All ten ops 0..9 are valid (FTAR_MAXLOC / FTAR_MINLOC:
+     * FTAR_ERR_OP; ops 10..15 and 18..: FTAR_ERR_ARG).  With w the element's width in bits:
+     *   SUM / PROD         wrap modulo 2^w, signed and unsigned alike (two's complement), as
+     *                      FTAR_INT32 / FTAR_INT64 do; nothing saturates.
+     *   MAX / MIN          (x > y) ? x : y and (x < y) ? x : y, compared in the type's own
+     *                      signedness (0x80 is -128 as FTAR_INT8 and 128 as FTAR_UINT8).
+     *   LAND / LOR / LXOR  0 or 1, an operand counting as true when any of its bits is set.
+     *   BAND / BOR / BXOR  act on the bits.
+     * Every op is exactly associative and commutative on these types, so every form of a schedule
+     * and every recovery replay gives the same bits, and the _host pipeline may chunk.  Buffers
+     * need the element's own alignment only (1, 2, 4 or 8 bytes): a 1-byte buffer, and a 1-byte
+     * entry of ftar_allreduce_multi, may start at any address.  ftar_allreduce_multi_acc32 refuses
+     * them like every type that is not a 2-byte float. */
+    FTAR_INT8 = 48,   /* MPI_INT8_T, MPI_SIGNED_CHAR */
+    FTAR_UINT8 = 49,  /* MPI_UINT8_T, MPI_UNSIGNED_CHAR, MPI_BYTE */
+    FTAR_INT16 = 50,  /* MPI_INT16_T, MPI_SHORT */
+    FTAR_UINT16 = 51, /* MPI_UINT16_T, MPI_UNSIGNED_SHORT */
+    FTAR_UINT32 = 52, /* MPI_UINT32_T, MPI_UNSIGNED */
+    FTAR_UINT64 = 53  /* MPI_UINT64_T, MPI_UNSIGNED_LONG (LP64) */
 } ftar_dtype;
 
 typedef struct { float v; int32_t i; } ftar_float_int;
