@@ -22,8 +22,8 @@ inline bool op_known(int op) { return (op >= 0 && op < kNumOps) || op == kMaxloc
 // one width, signed and unsigned integers give identical bits for SUM and PROD (modulo 2^w) and
 // for the logical and bitwise ops; only MAX / MIN compare.  So each width has ONE type with all
 // ten ops (uint8_t, uint16_t, int32_t, int64_t) and its sibling is instantiated for MAX / MIN
-// alone.  Every dtype dispatcher of ftar_kernels.hip switches on this.  Never across widths: the
-// planners derive heads, tails and vector counts from the element size.
+// alone.  The one dtype dispatcher of ftar_kernels.hip (with_type) switches on this.  Never across
+// widths: the planners (ftar_plan.cpp) derive heads, tails and vector counts from the element size.
 inline int canon_dtype(int dtype, int op)
 {
     const bool order = op == kMax || op == kMin;
@@ -39,6 +39,12 @@ enum { kCopy = 0, kReduce = 1 };
 
 constexpr int kMaxKSegs = 48; // 16 user segments x (head, body, tail); 2.3 KB of kernarg
 constexpr int kTileVecs = 1024; // 16-byte vectors per workgroup tile (256 threads x 4)
+constexpr int kBlock = 256; // threads per workgroup: the kernels (ftar_kernels.hip) and the planners (ftar_plan.cpp)
+// 4 x 16 B per lane and operand (16 KiB per operand per workgroup): 6.49-6.50 TB/s on
+// rotating buffers with nt stores against 6.14-6.20 for 2 and 6.05-6.09 for 8
+// (tools/hbm_sweep.hip, profiles/r02/hbm_sweep_focused.txt)
+constexpr int kUnroll = 4;
+static_assert(kBlock * kUnroll == kTileVecs, "tile size");
 constexpr int kChunkTiles = 8; // tiles per chunk of the interleaved block mapping (128 KiB)
 constexpr int kMaxIleave = 16; // vector pieces that can share the interleaved prefix
 

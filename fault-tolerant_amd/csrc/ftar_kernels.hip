@@ -198,6 +198,33 @@ static hipError_t with_op(int op, Fn &&fn)
     }
 }
 
+// Runs fn(type_tag<T>) for the runtime dtype: T is the element type whose instantiation computes
+// `op` on `dtype` (canon_dtype, ftar_kernels.h).  The one dtype switch of the launchers below;
+// with_op<T> inside fn then picks the op.
+template <typename T> struct type_tag { using type = T; };
+template <typename Fn>
+static hipError_t with_type(int dtype, int op, Fn &&fn)
+{
+    switch (canon_dtype(dtype, op)) {
+    case kInt32: return fn(type_tag<int32_t>{});
+    case kFloat32: return fn(type_tag<float>{});
+    case kInt64: return fn(type_tag<int64_t>{});
+    case kFloat64: return fn(type_tag<double>{});
+    case kFloat16: return fn(type_tag<f16_t>{});
+    case kBFloat16: return fn(type_tag<bf16_t>{});
+    case kFloatInt: return fn(type_tag<fi_t>{});
+    case k2Int: return fn(type_tag<ii_t>{});
+    case kDoubleInt: return fn(type_tag<di_t>{});
+    case kInt8: return fn(type_tag<int8_t>{});
+    case kUInt8: return fn(type_tag<uint8_t>{});
+    case kInt16: return fn(type_tag<int16_t>{});
+    case kUInt16: return fn(type_tag<uint16_t>{});
+    case kUInt32: return fn(type_tag<uint32_t>{});
+    case kUInt64: return fn(type_tag<uint64_t>{});
+    default: return hipErrorInvalidValue;
+    }
+}
+
 // The 8- and 16-bit integers' vector path, one 32-bit register (two or four elements) at a time.
 // gfx950 has packed 16-bit integer add, mul_lo, max, min and shifts (v_pk_*_u16 / _i16, reached
 // through ext_vector_type arithmetic and the elementwise builtins) and no packed 8-bit ALU at all:
@@ -385,12 +412,7 @@ FTAR_APPLY16_LOC16(kMinloc)
 // ---------------------------------------------------------------------------------
 // segment kernel
 // ---------------------------------------------------------------------------------
-constexpr int kBlock = 256;
-// 4 x 16 B per lane and operand (16 KiB per operand per workgroup): 6.49-6.50 TB/s on
-// rotating buffers with nt stores against 6.14-6.20 for 2 and 6.05-6.09 for 8
-// (tools/hbm_sweep.hip, profiles/r02/hbm_sweep_focused.txt)
-constexpr int kUnroll = 4;
-static_assert(kBlock * kUnroll == kTileVecs, "tile size");
+// (kBlock threads per workgroup, kUnroll vectors per lane and operand: ftar_kernels.h)
 
 // Streaming operands are read once and results are not re-read by this kernel:
 // non-temporal loads AND stores (global_load/store_dwordx4 ... nt).  Timed on rotating
@@ -761,32 +783,8 @@ __global__ __launch_bounds__(kBlock) void tree_batch_kernel(TreeBatch B)
 }
 
 // ---------------------------------------------------------------------------------
-// host-side dispatch
+// host-side dispatch (the planners of these launches: ftar_plan.cpp)
 // ---------------------------------------------------------------------------------
-unsigned plan_tree(TreeArgs *A, int p, size_t esize, unsigned max_blocks)
-{
-    uintptr_t mis = (uintptr_t)A->out & 15;
-    bool co = (16 % esize == 0) && (mis % esize == 0);
-    for (int j = 0; j < p; j++) co = co && (((uintptr_t)A->src[j] & 15) == mis);
-    for (int o = 0; o < A->nmore; o++) co = co && (((uintptr_t)A->more[o] & 15) == mis);
-    A->head = A->nv = 0;
-    if (co) {
-        size_t head = mis ? (16 - mis) / esize : 0;
-        if (head > A->n) head = A->n;
-        A->head = head;
-        A->nv = (A->n - head) * esize / 16;
-    }
-    size_t nscalar = A->n - A->nv * (16 / esize);
-    const unsigned u = (A->unroll == 2 || A->unroll == 4) && (p == 4 || p == 8) ? A->unroll : 1;
-    A->unroll = u;
-    size_t vb = (A->nv + (size_t)kBlock * u - 1) / ((size_t)kBlock * u);
-    if (vb > max_blocks) return 0; // the caller splits larger blocks
-    size_t sb = (nscalar + kBlock - 1) / kBlock;
-    if (sb > 256) sb = 256;
-    A->nvb = (unsigned)vb;
-    return (unsigned)(vb + sb);
-}
-
 template <typename T, int OP, int P>
 static void launch_tree_u(const TreeArgs &A, unsigned grid, hipStream_t s)
 {
@@ -816,74 +814,12 @@ static hipError_t launch_tree_op(int p, const TreeArgs &A, unsigned grid, hipStr
     return hipGetLastError();
 }
 
-template <typename T>
-static hipError_t launch_tree_t(int op, int p, const TreeArgs &A, unsigned grid, hipStream_t s)
-{
-    return with_op<T>(op, [&](auto o) { return launch_tree_op<T, decltype(o)::value>(p, A, grid, s); });
-}
-
 hipError_t launch_tree(int dtype, int op, int p, const TreeArgs &A, unsigned grid, hipStream_t s)
 {
-    switch (canon_dtype(dtype, op)) {
-    case kInt32: return launch_tree_t<int32_t>(op, p, A, grid, s);
-    case kFloat32: return launch_tree_t<float>(op, p, A, grid, s);
-    case kInt64: return launch_tree_t<int64_t>(op, p, A, grid, s);
-    case kFloat64: return launch_tree_t<double>(op, p, A, grid, s);
-    case kFloat16: return launch_tree_t<f16_t>(op, p, A, grid, s);
-    case kBFloat16: return launch_tree_t<bf16_t>(op, p, A, grid, s);
-    case kFloatInt: return launch_tree_t<fi_t>(op, p, A, grid, s);
-    case k2Int: return launch_tree_t<ii_t>(op, p, A, grid, s);
-    case kDoubleInt: return launch_tree_t<di_t>(op, p, A, grid, s);
-    case kInt8: return launch_tree_t<int8_t>(op, p, A, grid, s);
-    case kUInt8: return launch_tree_t<uint8_t>(op, p, A, grid, s);
-    case kInt16: return launch_tree_t<int16_t>(op, p, A, grid, s);
-    case kUInt16: return launch_tree_t<uint16_t>(op, p, A, grid, s);
-    case kUInt32: return launch_tree_t<uint32_t>(op, p, A, grid, s);
-    case kUInt64: return launch_tree_t<uint64_t>(op, p, A, grid, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-unsigned plan_tree_batch(TreeBatch *B, int p, size_t esize, unsigned max_blocks)
-{
-    unsigned total = 0;
-    for (int k = 0; k < B->nt; k++) {
-        B->first[k] = total;
-        B->t[k].unroll = 1; // tree_batch_kernel is instantiated for one vector per lane and source
-        unsigned g = plan_tree(&B->t[k], p, esize, max_blocks);
-        if (g == 0) return 0;
-        total += g;
-    }
-    B->first[B->nt] = total;
-    return total;
-}
-
-unsigned cap_tree_batch(TreeBatch *B, unsigned max_total)
-{
-    unsigned sb = 0, vb = 0, trees_v = 0;
-    for (int k = 0; k < B->nt; k++) {
-        vb += B->t[k].nvb;
-        sb += B->first[k + 1] - B->first[k] - B->t[k].nvb;
-        trees_v += B->t[k].nvb > 0;
-    }
-    if (vb + sb <= max_total) return vb + sb;
-    if (sb + trees_v > max_total) return 0;
-    const unsigned avail = max_total - sb;
-    unsigned nvb[kMaxBatch], total = 0;
-    for (int k = 0; k < B->nt; k++) {
-        nvb[k] = B->t[k].nvb ? (unsigned)((unsigned long long)B->t[k].nvb * avail / vb) : 0;
-        if (B->t[k].nvb && nvb[k] < 1) nvb[k] = 1;
-        total += nvb[k] + (B->first[k + 1] - B->first[k] - B->t[k].nvb);
-    }
-    if (total > max_total) return 0; // unchanged
-    total = 0;
-    for (int k = 0; k < B->nt; k++) {
-        const unsigned s = B->first[k + 1] - B->first[k] - B->t[k].nvb;
-        B->first[k] = total;
-        B->t[k].nvb = nvb[k];
-        total += nvb[k] + s;
-    }
-    B->first[B->nt] = total;
-    return total;
+    return with_type(dtype, op, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return with_op<T>(op, [&](auto o) { return launch_tree_op<T, decltype(o)::value>(p, A, grid, s); });
+    });
 }
 
 template <typename T, int OP>
@@ -898,40 +834,11 @@ static hipError_t launch_batch_op(int p, const TreeBatch &B, unsigned grid, hipS
     return hipGetLastError();
 }
 
-template <typename T>
-static hipError_t launch_batch_t(int op, int p, const TreeBatch &B, unsigned grid, hipStream_t s)
-{
-    return with_op<T>(op, [&](auto o) { return launch_batch_op<T, decltype(o)::value>(p, B, grid, s); });
-}
-
 hipError_t launch_tree_batch(int dtype, int op, int p, const TreeBatch &B, unsigned grid, hipStream_t s)
 {
-    switch (canon_dtype(dtype, op)) {
-    case kInt32: return launch_batch_t<int32_t>(op, p, B, grid, s);
-    case kFloat32: return launch_batch_t<float>(op, p, B, grid, s);
-    case kInt64: return launch_batch_t<int64_t>(op, p, B, grid, s);
-    case kFloat64: return launch_batch_t<double>(op, p, B, grid, s);
-    case kFloat16: return launch_batch_t<f16_t>(op, p, B, grid, s);
-    case kBFloat16: return launch_batch_t<bf16_t>(op, p, B, grid, s);
-    case kFloatInt: return launch_batch_t<fi_t>(op, p, B, grid, s);
-    case k2Int: return launch_batch_t<ii_t>(op, p, B, grid, s);
-    case kDoubleInt: return launch_batch_t<di_t>(op, p, B, grid, s);
-    case kInt8: return launch_batch_t<int8_t>(op, p, B, grid, s);
-    case kUInt8: return launch_batch_t<uint8_t>(op, p, B, grid, s);
-    case kInt16: return launch_batch_t<int16_t>(op, p, B, grid, s);
-    case kUInt16: return launch_batch_t<uint16_t>(op, p, B, grid, s);
-    case kUInt32: return launch_batch_t<uint32_t>(op, p, B, grid, s);
-    case kUInt64: return launch_batch_t<uint64_t>(op, p, B, grid, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <typename T>
-static hipError_t launch_t(int op, const KSegList &L, unsigned grid, hipStream_t s)
-{
-    return with_op<T>(op, [&](auto o) {
-        hipLaunchKernelGGL((segment_kernel<T, decltype(o)::value>), dim3(grid), dim3(kBlock), 0, s, L);
-        return hipGetLastError();
+    return with_type(dtype, op, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return with_op<T>(op, [&](auto o) { return launch_batch_op<T, decltype(o)::value>(p, B, grid, s); });
     });
 }
 
@@ -1257,34 +1164,12 @@ hipError_t launch_gather_cvt(const GatherArgs &A, int dtype, float scale, int sc
 
 hipError_t launch_segments(int dtype, int op, const KSegList &L, unsigned grid, hipStream_t s)
 {
-    switch (canon_dtype(dtype, op)) {
-    case kInt32: return launch_t<int32_t>(op, L, grid, s);
-    case kFloat32: return launch_t<float>(op, L, grid, s);
-    case kInt64: return launch_t<int64_t>(op, L, grid, s);
-    case kFloat64: return launch_t<double>(op, L, grid, s);
-    case kFloat16: return launch_t<f16_t>(op, L, grid, s);
-    case kBFloat16: return launch_t<bf16_t>(op, L, grid, s);
-    case kFloatInt: return launch_t<fi_t>(op, L, grid, s);
-    case k2Int: return launch_t<ii_t>(op, L, grid, s);
-    case kDoubleInt: return launch_t<di_t>(op, L, grid, s);
-    case kInt8: return launch_t<int8_t>(op, L, grid, s);
-    case kUInt8: return launch_t<uint8_t>(op, L, grid, s);
-    case kInt16: return launch_t<int16_t>(op, L, grid, s);
-    case kUInt16: return launch_t<uint16_t>(op, L, grid, s);
-    case kUInt32: return launch_t<uint32_t>(op, L, grid, s);
-    case kUInt64: return launch_t<uint64_t>(op, L, grid, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <typename T>
-static hipError_t launch_lds_t(int op, uint4 *inout, const uint4 *in, size_t nv, unsigned grid, hipStream_t s,
-                               unsigned nts)
-{
-    return with_op<T>(op, [&](auto o) {
-        hipLaunchKernelGGL((reduce_lds_kernel<T, decltype(o)::value>), dim3(grid), dim3(kBlock), 0, s, inout, in, nv,
-                           nts);
-        return hipGetLastError();
+    return with_type(dtype, op, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return with_op<T>(op, [&](auto o) {
+            hipLaunchKernelGGL((segment_kernel<T, decltype(o)::value>), dim3(grid), dim3(kBlock), 0, s, L);
+            return hipGetLastError();
+        });
     });
 }
 
@@ -1293,145 +1178,14 @@ hipError_t launch_reduce_lds(int dtype, int op, void *inout, const void *in, siz
 {
     uint4 *io = (uint4 *)inout;
     const uint4 *i = (const uint4 *)in;
-    switch (canon_dtype(dtype, op)) {
-    case kInt32: return launch_lds_t<int32_t>(op, io, i, nvec, grid, s, nts);
-    case kFloat32: return launch_lds_t<float>(op, io, i, nvec, grid, s, nts);
-    case kInt64: return launch_lds_t<int64_t>(op, io, i, nvec, grid, s, nts);
-    case kFloat64: return launch_lds_t<double>(op, io, i, nvec, grid, s, nts);
-    case kFloat16: return launch_lds_t<f16_t>(op, io, i, nvec, grid, s, nts);
-    case kBFloat16: return launch_lds_t<bf16_t>(op, io, i, nvec, grid, s, nts);
-    case kFloatInt: return launch_lds_t<fi_t>(op, io, i, nvec, grid, s, nts);
-    case k2Int: return launch_lds_t<ii_t>(op, io, i, nvec, grid, s, nts);
-    case kDoubleInt: return launch_lds_t<di_t>(op, io, i, nvec, grid, s, nts);
-    case kInt8: return launch_lds_t<int8_t>(op, io, i, nvec, grid, s, nts);
-    case kUInt8: return launch_lds_t<uint8_t>(op, io, i, nvec, grid, s, nts);
-    case kInt16: return launch_lds_t<int16_t>(op, io, i, nvec, grid, s, nts);
-    case kUInt16: return launch_lds_t<uint16_t>(op, io, i, nvec, grid, s, nts);
-    case kUInt32: return launch_lds_t<uint32_t>(op, io, i, nvec, grid, s, nts);
-    case kUInt64: return launch_lds_t<uint64_t>(op, io, i, nvec, grid, s, nts);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-// Split user segments into co-aligned vector bodies + scalar heads/tails and assign
-// blocks.  Returns the grid size (0 if there is nothing to do).
-unsigned plan_segments(const SegIn *in, int nin, size_t esize, unsigned max_blocks, KSegList *L)
-{
-    L->nseg = 0;
-    L->nt_store = 0;
-    L->sig = KSignal{nullptr, nullptr, 0, 0};
-    size_t vec_bytes_total = 0;
-    struct Piece { KSeg k; size_t bytes; } pieces[kMaxKSegs];
-    int np = 0;
-    for (int s = 0; s < nin; s++) {
-        const SegIn &g = in[s];
-        if (g.n == 0) continue;
-        uintptr_t ao = (uintptr_t)g.out, ax = (uintptr_t)g.x, ay = (uintptr_t)(g.kind == kCopy ? g.x : g.y);
-        uintptr_t ao2 = g.out2 ? (uintptr_t)g.out2 : ao;
-        bool co = ((ao & 15) == (ax & 15)) && ((ao & 15) == (ay & 15)) && ((ao & 15) == (ao2 & 15)) &&
-                  (16 % esize == 0) && ((ao & 15) % esize == 0);
-        size_t head = 0, body = 0;
-        if (co) {
-            size_t mis = ao & 15;
-            head = mis ? (16 - mis) / esize : 0;
-            if (head > g.n) head = g.n;
-            size_t rest = g.n - head;
-            size_t epv = 16 / esize;
-            body = (rest / epv) * epv;
-        }
-        size_t tail_off = head + body;
-        auto add = [&](size_t off, size_t n, unsigned vec) {
-            if (n == 0) return;
-            KSeg k;
-            k.out = (char *)g.out + off * esize;
-            k.out2 = g.out2 ? (void *)((char *)g.out2 + off * esize) : nullptr;
-            k.x = (const char *)g.x + off * esize;
-            k.y = g.kind == kCopy ? k.x : (const void *)((const char *)g.y + off * esize);
-            k.n = n;
-            k.kind = (unsigned)g.kind;
-            k.vec = vec;
-            k.blk_begin = k.blk_end = 0;
-            pieces[np].k = k;
-            pieces[np].bytes = n * esize;
-            if (vec) vec_bytes_total += n * esize;
-            np++;
-        };
-        add(0, head, 0);
-        add(head, body, 1);
-        add(tail_off, g.n - tail_off, 0);
-    }
-    if (np == 0) return 0;
-    const size_t tile_bytes = (size_t)kBlock * 16 * kUnroll;
-    size_t total_tiles = 0;
-    for (int i = 0; i < np; i++)
-        if (pieces[i].k.vec) total_tiles += (pieces[i].bytes + tile_bytes - 1) / tile_bytes;
-    L->nil = 0;
-    L->il_blocks = 0;
-    if (total_tiles + 64 * (size_t)np <= max_blocks) {
-        // uncapped grid: one block per tile.  Vector pieces of at least one chunk share
-        // an interleaved prefix of `rounds` chunks each (the shortest one's length).
-        size_t rounds = SIZE_MAX;
-        unsigned char il[kMaxIleave];
-        int nil = 0;
-        for (int i = 0; i < np && nil < kMaxIleave; i++) {
-            if (!pieces[i].k.vec) continue;
-            size_t t = (pieces[i].bytes + tile_bytes - 1) / tile_bytes;
-            if (t < (size_t)kChunkTiles) continue;
-            il[nil++] = (unsigned char)i;
-            if (t / kChunkTiles < rounds) rounds = t / kChunkTiles;
-        }
-        if (nil >= 2) {
-            L->nil = nil;
-            L->il_blocks = (unsigned)(rounds * kChunkTiles * nil);
-            memcpy(L->il, il, sizeof(il));
-        } else {
-            rounds = 0;
-        }
-        unsigned next = L->il_blocks;
-        for (int i = 0; i < np; i++) {
-            KSeg &k = pieces[i].k;
-            bool in_il = false;
-            for (int t = 0; t < L->nil; t++) in_il |= (L->il[t] == i);
-            size_t tiles = k.vec ? (pieces[i].bytes + tile_bytes - 1) / tile_bytes : 0;
-            size_t base = in_il ? rounds * kChunkTiles : 0;
-            size_t want = k.vec ? tiles - base : (k.n + kBlock - 1) / kBlock;
-            if (!k.vec && want > 64) want = 64;
-            k.ntiles = (unsigned)tiles;
-            k.tile_base = (unsigned)base;
-            k.blk_begin = next;
-            k.blk_end = next + (unsigned)want;
-            next = k.blk_end;
-            L->s[L->nseg++] = k;
-        }
-        return next;
-    }
-    // capped grid (more than max_blocks tiles): blocks split between the pieces in
-    // proportion to their bytes, pieces loop with a block stride; scalar pieces (heads/
-    // tails < 16 B, or non-co-aligned slow paths) get up to 64 blocks.
-    unsigned next = 0;
-    for (int i = 0; i < np; i++) {
-        KSeg &k = pieces[i].k;
-        size_t want;
-        if (k.vec) {
-            size_t need = (pieces[i].bytes + tile_bytes - 1) / tile_bytes;
-            size_t share = vec_bytes_total ? (size_t)((double)max_blocks * (double)pieces[i].bytes /
-                                                     (double)vec_bytes_total) + 1
-                                           : 1;
-            want = need < share ? need : share;
-            k.ntiles = (unsigned)need;
-        } else {
-            size_t need = (k.n + kBlock - 1) / kBlock;
-            want = need < 64 ? need : 64;
-            k.ntiles = 0;
-        }
-        if (want < 1) want = 1;
-        k.tile_base = 0;
-        k.blk_begin = next;
-        k.blk_end = next + (unsigned)want;
-        next = k.blk_end;
-        L->s[L->nseg++] = k;
-    }
-    return next;
+    return with_type(dtype, op, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return with_op<T>(op, [&](auto o) {
+            hipLaunchKernelGGL((reduce_lds_kernel<T, decltype(o)::value>), dim3(grid), dim3(kBlock), 0, s, io, i, nvec,
+                               nts);
+            return hipGetLastError();
+        });
+    });
 }
 
 } // namespace ftar

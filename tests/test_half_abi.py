@@ -5,7 +5,7 @@
 * the host-sim test library, whose device layer reduces the four original types only, refuses
   them at the boundary instead of running them as something else;
 * the Python binding maps the two torch dtypes;
-* the work plans cover every element exactly once at 2-byte elements (tests/kernel_plan16, a
+* the work plans cover every element exactly once at 2-byte elements (tests/kernel_plan, a
   host program built with the address and undefined-behaviour sanitizers);
 * half_model.py's restatement of the no-fault reduction trees -- which the GPU test reuses
   with 16-bit rounding -- is bit-equal to the oracle on float32.
@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import half_model as M
+from plan_checks import run_planwalk
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F16, BF16 = 16, 17
@@ -90,18 +91,11 @@ def test_hostsim_refuses_the_half_types(hostsim, monkeypatch):
         L.ftar_finalize(h)
 
 
-def test_plans_cover_two_byte_elements(built):
-    """tests/kernel_plan16: plan_segments, plan_tree and plan_tree_batch at esize 2, every
-    misalignment of 0..7 elements, co-aligned and not; its own process, under ASan + UBSan."""
-    d = os.path.join(ROOT, "tests", "kernel_plan16")
-    subprocess.run(["make", "-s", "-C", d], check=True)
-    exe = os.path.join(d, "_build", "plan16_check")
-    flags = subprocess.run(["nm", exe], capture_output=True, text=True, check=True).stdout
-    assert "__asan_init" in flags and "__ubsan_handle" in flags  # really built with the sanitizers
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")  # (the HIP runtime's start-up allocations)
-    cp = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
-    assert cp.returncode == 0, cp.stdout + cp.stderr[-3000:]
-    assert cp.stdout.startswith("OK ") and int(cp.stdout.split()[1]) > 10000
+def test_plans_cover_two_byte_elements():
+    """tests/kernel_plan at esize 2: plan_segments, plan_tree and plan_tree_batch, every misalignment
+    of 0..7 elements, co-aligned and not; plain, and with checker and planners under ASan + UBSan.
+    At least the 28468 cases of the walker this type came with."""
+    assert run_planwalk(2) >= 28468
 
 
 def _f32_pair(op):

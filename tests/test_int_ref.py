@@ -5,9 +5,9 @@ tests/int_types/ref_check is a host program (no HIP call): `apply` runs the refe
 files, `selftest` generates the inputs of every case of int_check and asserts that they tell a
 right kernel from the wrong ones a packed or SWAR implementation can be (signedness of the compare
 swapped, saturating instead of wrapping, a carry leaking into the neighbouring element, a product's
-upper half kept, a logical result other than 0 / 1), `planwalk` replays plan_segments, plan_tree,
-plan_tree_batch and gather_piece at 1- and 2-byte elements.  All three also run in a build with
-ASan + UBSan.
+upper half kept, a logical result other than 0 / 1), `planwalk` replays gather_piece at 1- and
+2-byte elements.  All three also run in a build with ASan + UBSan.  The planners (plan_segments,
+plan_tree, plan_tree_batch) at those sizes are walked by tests/kernel_plan.
 
 References here: numpy's fixed-width integer arithmetic (int_model.combine, overflow warnings off)
 * 8-bit: all 65 536 operand pairs x 10 ops x both signednesses;
@@ -25,16 +25,16 @@ import numpy as np
 import pytest
 
 import int_model as I
+from plan_checks import run_planwalk
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIR = os.path.join(ROOT, "tests", "int_types")
-SAN_ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")  # (the HIP runtime's start-up allocations: the planners' object)
+SAN_ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")  # (the HIP runtime's start-up allocations: hipcc links it)
 
 
 @pytest.fixture(scope="module")
 def ref_check():
-    """(plain, sanitized) builds of the program; the planners come from the product's kernel object."""
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "fault-tolerant_amd"), "-j8"], check=True)
+    """(plain, sanitized) builds of the program: header only, nothing of the product is linked."""
     os.makedirs(os.path.join(DIR, "_build"), exist_ok=True)
     with open(os.path.join(DIR, "_build", ".ref.lock"), "w") as lk:  # one build at a time (pytest-xdist workers)
         fcntl.flock(lk, fcntl.LOCK_EX)
@@ -90,10 +90,15 @@ def test_inputs_tell_a_wrong_kernel_from_a_right_one(ref_check):
 
 
 def test_plans_cover_one_and_two_byte_elements(ref_check):
+    """The planners at esize 1 and 2 (tests/kernel_plan) and the gather walk that stays here: at
+    least the cases of the one walk these types came with (367488 + 91916 planner cases, 20882
+    gather cases)."""
+    assert run_planwalk(1) >= 367488
+    assert run_planwalk(2) >= 91916
     for exe, env in ((ref_check[0], None), (ref_check[1], SAN_ENV)):
         cp = subprocess.run([exe, "planwalk"], capture_output=True, text=True, timeout=300, env=env)
         assert cp.returncode == 0, cp.stdout[-3000:] + cp.stderr[-3000:]
-        assert cp.stdout.startswith("planwalk OK ") and int(cp.stdout.split()[2]) > 100000, cp.stdout
+        assert cp.stdout.startswith("planwalk OK ") and int(cp.stdout.split()[2]) >= 20882, cp.stdout
 
 
 def test_reference_under_sanitizers(ref_check):

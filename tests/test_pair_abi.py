@@ -8,7 +8,7 @@ FTAR_DOUBLE_INT = 34) at the boundary, without a GPU.
 * the host-sim test library, whose device layer reduces the four original types only, refuses
   the pair types at the boundary and touches nothing;
 * the work plans cover every element exactly once at 8- and 16-byte elements
-  (tests/kernel_plan_pair: a host program, run plain and built with ASan + UBSan);
+  (tests/kernel_plan: a host program, run plain and built with ASan + UBSan);
 * pack_pairs / unpack_pairs round-trip on CPU tensors;
 * the GPU test's two references agree with each other: the oracle's int64 MAX / MIN over the
   keys that encode (value, index) decodes to what the pairwise rule gives in half_model.py's
@@ -21,6 +21,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+from plan_checks import run_planwalk
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLOAT_INT, TWO_INT, DOUBLE_INT = 32, 33, 34
@@ -131,20 +133,13 @@ def test_hostsim_refuses_the_pair_types(hostsim, monkeypatch):
         L.ftar_finalize(h)
 
 
-def test_plans_cover_pair_elements(built):
-    """tests/kernel_plan_pair: plan_segments, plan_tree and plan_tree_batch at esize 8 and 16,
-    windows at every misalignment the types' alignment allows, co-aligned and not: the plain
-    build, and once more as a stand-alone program whose host code is built with ASan + UBSan."""
-    d = os.path.join(ROOT, "tests", "kernel_plan_pair")
-    subprocess.run(["make", "-s", "-C", d], check=True)
-    san = os.path.join(d, "_build", "planpair_check_san")
-    flags = subprocess.run(["nm", san], capture_output=True, text=True, check=True).stdout
-    assert "__asan_init" in flags and "__ubsan_handle" in flags  # really built with the sanitizers
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")  # (the HIP runtime's start-up allocations)
-    for exe in (os.path.join(d, "_build", "planpair_check"), san):
-        cp = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
-        assert cp.returncode == 0, cp.stdout + cp.stderr[-3000:]
-        assert cp.stdout.startswith("OK ") and int(cp.stdout.split()[1]) > 5000
+def test_plans_cover_pair_elements():
+    """tests/kernel_plan at esize 8 and 16: plan_segments, plan_tree and plan_tree_batch, windows at
+    every misalignment the types' alignment allows, co-aligned and not: the plain build, and once
+    more as a stand-alone program built, planners included, with ASan + UBSan.  At least the
+    5280 + 1320 cases of the walker these types came with."""
+    assert run_planwalk(8) >= 5280
+    assert run_planwalk(16) >= 1320
 
 
 @pytest.mark.parametrize("dt", PAIRS)

@@ -14,7 +14,7 @@
 //               before the gate opens, the gated work only after
 // Prints one JSON line.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I fault-tolerant_amd/csrc tools/gate_probe.hip \
-//         fault-tolerant_amd/csrc/ftar_kernels.hip -o tools/_build/gate_probe
+//         fault-tolerant_amd/csrc/ftar_kernels.hip fault-tolerant_amd/csrc/ftar_plan.cpp -o tools/_build/gate_probe
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
