@@ -26,8 +26,18 @@ bool can_gate(const ftar_dev *d, unsigned grid)
 }
 
 // The gate fields of a launch about to be queued gated; its bytes are counted when it runs.
-ftar::KSignal arm_gate(ftar_dev *d, double link, double hbm)
+// With a staging request (stage_dst and stage_n set: copy stage_n elements of es bytes
+// before waiting at the gate) the launch raises the flag twice, staged, then done: the stage
+// tag is taken first, so it lies below the completion tag, the copy's bytes are counted now
+// (it runs whatever the gate's verdict), and the drain before the barrier waits for "staged".
+ftar::KSignal arm_gate(ftar_dev *d, double link, double hbm, void *stage_dst = nullptr,
+                       const void *stage_src = nullptr, size_t stage_n = 0, size_t es = 0)
 {
+    unsigned stage_tag = 0;
+    if (stage_dst && stage_n) {
+        stage_tag = ++d->sig_tag;
+        d->ctr.hbm_bytes += 2.0 * (double)stage_n * (double)es;
+    }
     d->gate_link = link;
     d->gate_hbm = hbm;
     d->pre_gate_any = d->signalled > 0;
@@ -46,18 +56,45 @@ ftar::KSignal arm_gate(ftar_dev *d, double link, double hbm)
     k.gate_val = 2u * d->gate_seq;
     k.err = gate_err(d, d->gate_seq);
     k.gate_ticks = d->gate_ticks;
+    if (stage_tag) {
+        k.stage_src = stage_src;
+        k.stage_dst = stage_dst;
+        k.stage_n = stage_n;
+        k.stage_es = (unsigned)es;
+        k.stage_tag = stage_tag;
+        k.stage_cnt = d->sig_cnt + 16; // its own counter, 64 B from the completion counter
+        d->pre_gate_any = 1;
+        d->pre_gate_tag = stage_tag;
+    }
     return k;
 }
 
-// A short gated launch of several workgroups waits with ONE of them polling the host word
-// over PCIe, the others polling the device word it relays the verdict through (the relayed
-// form of the mid-size launches, signal_gate): up to 64 uncached PCIe pollers per launch
-// slowed the peers sharing a GPU 2x at 1 MiB (RD, 4 ranks: 194 vs 93 us ungated).
+// The relayed gate of the launch just armed: ONE workgroup polls the host word over PCIe and
+// passes the verdict on through the slot's two device words (election, verdict; signal_gate).
+void relay_words(ftar_dev *d, ftar::KSignal &sig)
+{
+    sig.gate_poll = d->gate_dw + d->gate_seq % ftar::kGateSlots;
+    sig.gate_dev = sig.gate_poll + 32;
+}
+
+// A short gated launch of several workgroups waits relayed, like the mid-size launches: up
+// to 64 uncached PCIe pollers per launch slowed the peers sharing a GPU 2x at 1 MiB (RD,
+// 4 ranks: 194 vs 93 us ungated).
 void relay_gate(ftar_dev *d, ftar::KSignal &sig, unsigned grid)
 {
-    if (!d->gate_dw || grid < d->relay_min) return;
-    sig.gate_poll = d->gate_dw + d->gate_seq % ftar::kGateSlots;
-    sig.gate_dev = d->gate_dw + 32 + d->gate_seq % ftar::kGateSlots;
+    if (d->gate_dw && grid >= d->relay_min) relay_words(d, sig);
+}
+
+// The trace of the gated launch just armed (FTAR_TRACE): its line, with the region staged
+// before the gate, and its regions' text kept with the plan for a relaunch's line.
+void trace_gated(ftar_dev *d, const ftar::KSignal &sig, const std::vector<TrRange> &rd, const std::vector<TrRange> &wr)
+{
+    const std::string rw = tr_rw(d, rd, wr);
+    d->gp[d->gate_seq & 1].tr_rw = rw;
+    std::string st;
+    if (sig.stage_tag) tr_fmt(d, {{sig.stage_dst, sig.stage_n * sig.stage_es}}, st);
+    d->tr_fenced = 0;
+    tr_launch(d, d->stream, &sig, rw, d->gate_seq, "k", st, sig.stage_tag);
 }
 
 // Keep the plan of the gate just armed (d->gate_seq) for a relaunch: the same launch with
@@ -112,35 +149,13 @@ int fdev_tree_batch_staged_gated(ftar_dev *d, int dtype, int op, const void *con
         for (int k = 0; k < B.nt; k++)
             for (int j = 0; j < nsrc; j++)
                 if (overlaps(B.t[t].out, B.t[t].n * es, B.t[k].src[j], B.t[k].n * es)) return 0;
-    unsigned stage_tag = 0;
-    if (stage_dst && stage_n) {
-        stage_tag = ++d->sig_tag; // the launch raises the flag twice: staged, then done
-        d->ctr.hbm_bytes += 2.0 * (double)stage_n * (double)es;
-    }
-    B.sig = arm_gate(d, link, hbm);
+    B.sig = arm_gate(d, link, hbm, stage_dst, stage_src, stage_n, es);
     relay_gate(d, B.sig, grid);
     keep_plan(d, 1, dtype, op, nsrc, grid, nullptr, &B);
-    if (stage_tag) {
-        B.sig.stage_src = stage_src;
-        B.sig.stage_dst = stage_dst;
-        B.sig.stage_n = stage_n;
-        B.sig.stage_es = (unsigned)esize_of(dtype);
-        B.sig.stage_tag = stage_tag;
-        B.sig.stage_cnt = d->sig_cnt + 16; // its own counter, 64 B from the completion counter
-        d->pre_gate_any = 1;               // the drain before the barrier waits for "staged"
-        d->pre_gate_tag = stage_tag;
-    }
     if (d->trace) {
-        std::vector<TrRange> rd, wr, sw;
+        std::vector<TrRange> rd, wr;
         batch_ranges(B, nsrc, es, rd, wr);
-        const std::string rw = tr_rw(d, rd, wr);
-        d->gp[d->gate_seq & 1].tr_rw = rw;
-        std::string st;
-        if (stage_tag) {
-            sw.push_back({stage_dst, stage_n * es});
-            tr_fmt(d, sw, st);
-        }
-        tr_launch(d, d->stream, &B.sig, rw, d->gate_seq, "k", st, stage_tag);
+        trace_gated(d, B.sig, rd, wr);
     }
     hipError_t e = ftar::launch_tree_batch(dtype, op, nsrc, B, grid, d->stream);
     if (e != hipSuccess) return set_err(e, "tree_batch_kernel launch (gated)");
@@ -193,8 +208,8 @@ namespace fdevi {
 // big_blocks workgroups (each loops over its share of tiles: a waiting launch occupies a
 // part of the device, so ranks sharing a GPU still run), its gate relayed through device
 // words.  It does not signal: after the gate opens it is drained by a fenced marker.
-int run_gated_relayed(ftar_dev *d, int dtype, int op, const ftar::SegIn *in, int nseg, size_t es, double link,
-                      double hbm, int *gated)
+int run_gated_relayed(ftar_dev *d, int dtype, int op, const fdev_seg *segs, const ftar::SegIn *in, int nseg, size_t es,
+                      double link, double hbm, int *gated)
 {
     if (!d->flag_sync || !d->gate_dw || d->profiling || d->gate_pending) return 0;
     ftar::KSegList L;
@@ -208,21 +223,12 @@ int run_gated_relayed(ftar_dev *d, int dtype, int op, const ftar::SegIn *in, int
     d->signalled--; // arm_gate counted a signalled launch: this one drains through a marker
     L.sig.cnt = nullptr;
     L.sig.flag = nullptr;
-    L.sig.gate_poll = d->gate_dw + d->gate_seq % ftar::kGateSlots;
-    L.sig.gate_dev = d->gate_dw + 32 + d->gate_seq % ftar::kGateSlots;
+    relay_words(d, L.sig);
     keep_plan(d, 0, dtype, op, 0, grid, &L, nullptr);
     if (d->trace) {
         std::vector<TrRange> rd, wr;
-        for (int i = 0; i < nseg; i++) {
-            rd.push_back({in[i].x, in[i].n * es});
-            if (in[i].kind != ftar::kCopy) rd.push_back({in[i].y, in[i].n * es});
-            wr.push_back({in[i].out, in[i].n * es});
-            wr.push_back({in[i].out2, in[i].n * es});
-        }
-        const std::string rw = tr_rw(d, rd, wr);
-        d->gp[d->gate_seq & 1].tr_rw = rw;
-        d->tr_fenced = 0;
-        tr_launch(d, d->stream, &L.sig, rw, d->gate_seq, "k");
+        seg_ranges(segs, nseg, es, rd, wr);
+        trace_gated(d, L.sig, rd, wr);
     }
     hipError_t e = ftar::launch_segments(dtype, op, L, grid, d->stream);
     if (e != hipSuccess) return set_err(e, "segment_kernel launch (gated, relayed)");
@@ -241,10 +247,7 @@ int fdev_run_gated(ftar_dev *d, int dtype, int op, const fdev_seg *segs, int nse
 {
     *gated = 0;
     size_t es = esize_of(dtype);
-    if (es == 0 || !ftar::op_known(op) || nseg < 0 || nseg > FDEV_MAX_SEGS || tag < 0 || tag >= FDEV_NTAGS) {
-        snprintf(g_err, sizeof(g_err), "fdev_run_gated: bad arguments");
-        return 13;
-    }
+    if (int rc = check_args("fdev_run_gated", es, op, tag, nseg >= 0 && nseg <= FDEV_MAX_SEGS)) return rc;
     ftar::SegIn in[FDEV_MAX_SEGS];
     double link = 0, hbm = 0;
     seg_inputs(segs, nseg, es, in, &link, &hbm);
@@ -259,39 +262,16 @@ int fdev_run_gated(ftar_dev *d, int dtype, int op, const fdev_seg *segs, int nse
     ftar::KSegList L;
     unsigned grid = ftar::plan_segments(in, nseg, es, d->max_blocks, &L);
     if (grid > d->flag_max && !stage_dst)
-        return run_gated_relayed(d, dtype, op, in, nseg, es, link, hbm, gated);
+        return run_gated_relayed(d, dtype, op, segs, in, nseg, es, link, hbm, gated);
     if (!can_gate(d, grid)) return 0;
     L.nt_store = nt_store();
-    unsigned stage_tag = 0;
-    if (stage_dst && stage_n) {
-        stage_tag = ++d->sig_tag; // the launch raises the flag twice: staged, then done
-        d->ctr.hbm_bytes += 2.0 * (double)stage_n * (double)es;
-    }
-    L.sig = arm_gate(d, link, hbm);
+    L.sig = arm_gate(d, link, hbm, stage_dst, stage_src, stage_n, es);
     relay_gate(d, L.sig, grid);
     keep_plan(d, 0, dtype, op, 0, grid, &L, nullptr);
-    if (stage_tag) {
-        L.sig.stage_src = stage_src;
-        L.sig.stage_dst = stage_dst;
-        L.sig.stage_n = stage_n;
-        L.sig.stage_es = (unsigned)es;
-        L.sig.stage_tag = stage_tag;
-        L.sig.stage_cnt = d->sig_cnt + 16;
-        d->pre_gate_any = 1;
-        d->pre_gate_tag = stage_tag;
-    }
     if (d->trace) {
-        std::vector<TrRange> rd, wr, sw;
+        std::vector<TrRange> rd, wr;
         seg_ranges(segs, nseg, es, rd, wr);
-        const std::string rw = tr_rw(d, rd, wr);
-        d->gp[d->gate_seq & 1].tr_rw = rw;
-        std::string st;
-        if (stage_tag) {
-            sw.push_back({stage_dst, stage_n * es});
-            tr_fmt(d, sw, st);
-        }
-        d->tr_fenced = 0;
-        tr_launch(d, d->stream, &L.sig, rw, d->gate_seq, "k", st, stage_tag);
+        trace_gated(d, L.sig, rd, wr);
     }
     hipError_t e = ftar::launch_segments(dtype, op, L, grid, d->stream);
     if (e != hipSuccess) return set_err(e, "segment_kernel launch (gated)");

@@ -140,6 +140,7 @@ namespace fdevi {
 // ---- ftar_dev_launch.cpp
 int ensure_bg(ftar_dev *d);
 hipEvent_t get_event(ftar_dev *d);
+int check_args(const char *who, size_t es, int op, int tag, bool rest);
 void note_launch(ftar_dev *d, hipStream_t st, unsigned grid, bool can_signal, ftar::KSignal *sig);
 void seg_inputs(const fdev_seg *segs, int nseg, size_t es, ftar::SegIn *in, double *link, double *hbm);
 bool overlaps(const void *a, size_t na, const void *b, size_t nb);

@@ -39,6 +39,53 @@ hipEvent_t get_event(ftar_dev *d)
     return e;
 }
 
+// The profiling bracket of a launch or copy on `st`: timed_begin takes two pooled events and
+// records the first (nothing when profiling is off), timed_end records the second and leaves
+// the pair to harvest() under `tag`.  Where a site begins decides what its time includes
+// (fdev_tree_out: a fenced marker of note_launch; gather_launch: not the table's copy).
+struct Timed {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+};
+
+static Timed timed_begin(ftar_dev *d, hipStream_t st)
+{
+    Timed t;
+    if (d->profiling) {
+        t.e0 = get_event(d);
+        t.e1 = get_event(d);
+        if (t.e0) (void)hipEventRecord(t.e0, st);
+    }
+    return t;
+}
+
+static void timed_end(ftar_dev *d, hipStream_t st, const Timed &t, int tag)
+{
+    if (d->profiling && t.e0 && t.e1) {
+        (void)hipEventRecord(t.e1, st);
+        d->pending.push_back(Pending{t.e0, t.e1, tag});
+    }
+}
+
+// Orders `st` (the background or the D2H stream) after everything queued on the main stream.
+static int order_after_main(ftar_dev *d, hipStream_t st)
+{
+    hipEvent_t e = get_event(d);
+    if (!e) return set_err(hipErrorOutOfMemory, "hipEventCreate");
+    HIPCHK(hipEventRecord(e, d->stream));
+    HIPCHK(hipStreamWaitEvent(st, e, 0));
+    d->event_pool.push_back(e);
+    return 0;
+}
+
+// The element size, operator and tag of a launch, and what else its entry point `who` asks
+// of its arguments (`rest`): 0, or 13 with "<who>: bad arguments" for fdev_last_error().
+int check_args(const char *who, size_t es, int op, int tag, bool rest)
+{
+    if (es != 0 && ftar::op_known(op) && tag >= 0 && tag < FDEV_NTAGS && rest) return 0;
+    snprintf(g_err, sizeof(g_err), "%s: bad arguments", who);
+    return 13;
+}
+
 // Bookkeeping of every launch or copy on a stream of this rank.  On the main stream: a
 // launch of at most flag_max workgroups that may signal gets the completion signal
 // (returned in *sig).  After a signal drain no marker packet has invalidated the caches
@@ -109,10 +156,7 @@ bool overlaps(const void *a, size_t na, const void *b, size_t nb)
 int run_on(ftar_dev *d, hipStream_t st, int dtype, int op, const fdev_seg *segs, int nseg, int tag)
 {
     size_t es = esize_of(dtype);
-    if (es == 0 || !ftar::op_known(op) || nseg < 0 || nseg > FDEV_MAX_SEGS || tag < 0 || tag >= FDEV_NTAGS) {
-        snprintf(g_err, sizeof(g_err), "fdev_run: bad arguments");
-        return 13;
-    }
+    if (int rc = check_args("fdev_run", es, op, tag, nseg >= 0 && nseg <= FDEV_MAX_SEGS)) return rc;
     ftar::SegIn in[FDEV_MAX_SEGS];
     double link = 0, hbm = 0;
     seg_inputs(segs, nseg, es, in, &link, &hbm);
@@ -141,18 +185,10 @@ int run_on(ftar_dev *d, hipStream_t st, int dtype, int op, const fdev_seg *segs,
         tr_launch(d, st, &L.sig, tr_rw(d, rd, wr), 0, "k");
         if (behind_wait) d->pw_launch_n = d->tr_n;
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (d->profiling) {
-        e0 = get_event(d);
-        e1 = get_event(d);
-        if (e0) (void)hipEventRecord(e0, st);
-    }
+    const Timed t = timed_begin(d, st);
     hipError_t e = ftar::launch_segments(dtype, op, L, grid, st);
     if (e != hipSuccess) return set_err(e, "segment_kernel launch");
-    if (d->profiling && e0 && e1) {
-        (void)hipEventRecord(e1, st);
-        d->pending.push_back(Pending{e0, e1, tag});
-    }
+    timed_end(d, st, t, tag);
     return 0;
 }
 
@@ -170,22 +206,14 @@ int fdev_tree_out(ftar_dev *d, int dtype, int op, const void *const *src, int ns
                   void *const *more, int nmore, int more_remote, size_t n, int tag)
 {
     size_t es = esize_of(dtype);
-    if (es == 0 || !ftar::op_known(op) || tag < 0 || tag >= FDEV_NTAGS ||
-        !(nsrc == 2 || nsrc == 4 || nsrc == 8 || nsrc == 16) || nmore < 0 || nmore > ftar::kMaxMore) {
-        snprintf(g_err, sizeof(g_err), "fdev_tree: bad arguments");
-        return 13;
-    }
+    const bool shape_ok = (nsrc == 2 || nsrc == 4 || nsrc == 8 || nsrc == 16) && nmore >= 0 && nmore <= ftar::kMaxMore;
+    if (int rc = check_args("fdev_tree", es, op, tag, shape_ok)) return rc;
     if (n == 0) return 0;
     int nremote = __builtin_popcount(remote_mask & ((1u << nsrc) - 1));
     const int mr = more_remote ? nmore : 0; // extra destinations in peers' HBM, or in ours
     d->ctr.link_bytes += (double)n * (double)es * (nremote + mr);
     d->ctr.hbm_bytes += (double)n * (double)es * (nsrc - nremote + 1 + nmore - mr);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (d->profiling) {
-        e0 = get_event(d);
-        e1 = get_event(d);
-        if (e0) (void)hipEventRecord(e0, d->stream);
-    }
+    const Timed t = timed_begin(d, d->stream); // in front of note_launch: its fenced marker is timed too
     note_launch(d, d->stream, ~0u, false, nullptr);
     if (d->trace) {
         std::vector<TrRange> rd, wr;
@@ -215,10 +243,7 @@ int fdev_tree_out(ftar_dev *d, int dtype, int op, const void *const *src, int ns
         hipError_t e = ftar::launch_tree(dtype, op, nsrc, A, grid, d->stream);
         if (e != hipSuccess) return set_err(e, "tree_kernel launch");
     }
-    if (d->profiling && e0 && e1) {
-        (void)hipEventRecord(e1, d->stream);
-        d->pending.push_back(Pending{e0, e1, tag});
-    }
+    timed_end(d, d->stream, t, tag); // one pair for all the pieces
     return 0;
 }
 
@@ -233,11 +258,8 @@ int build_batch(ftar_dev *d, int dtype, int op, const void *const *src, int nsrc
                 double *link, double *hbm)
 {
     size_t es = esize_of(dtype);
-    if (es == 0 || !ftar::op_known(op) || tag < 0 || tag >= FDEV_NTAGS || ntree < 1 || ntree > ftar::kMaxBatch ||
-        !(nsrc == 2 || nsrc == 4 || nsrc == 8)) {
-        snprintf(g_err, sizeof(g_err), "fdev_tree_batch: bad arguments");
-        return 13;
-    }
+    const bool shape_ok = ntree >= 1 && ntree <= ftar::kMaxBatch && (nsrc == 2 || nsrc == 4 || nsrc == 8);
+    if (int rc = check_args("fdev_tree_batch", es, op, tag, shape_ok)) return rc;
     memset(B, 0, sizeof(*B));
     B->nt = 0;
     *link = *hbm = 0;
@@ -283,18 +305,10 @@ int fdev_tree_batch(ftar_dev *d, int dtype, int op, const void *const *src, int 
         batch_ranges(B, nsrc, esize_of(dtype), rd, wr);
         tr_launch(d, d->stream, &B.sig, tr_rw(d, rd, wr), 0, "k");
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (d->profiling) {
-        e0 = get_event(d);
-        e1 = get_event(d);
-        if (e0) (void)hipEventRecord(e0, d->stream);
-    }
+    const Timed t = timed_begin(d, d->stream);
     hipError_t e = ftar::launch_tree_batch(dtype, op, nsrc, B, grid, d->stream);
     if (e != hipSuccess) return set_err(e, "tree_batch_kernel launch");
-    if (d->profiling && e0 && e1) {
-        (void)hipEventRecord(e1, d->stream);
-        d->pending.push_back(Pending{e0, e1, tag});
-    }
+    timed_end(d, d->stream, t, tag);
     return 0;
 }
 
@@ -365,19 +379,11 @@ static int gather_launch(ftar_dev *d, void *packed, const fdev_gent *table, int 
     }
     // (behind note_launch: a fenced marker it queued stays in front of everything of this launch)
     HIPCHK(hipMemcpyAsync(dm, hm, (size_t)n * sizeof(ftar::GEntry), hipMemcpyHostToDevice, d->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (d->profiling) {
-        e0 = get_event(d);
-        e1 = get_event(d);
-        if (e0) (void)hipEventRecord(e0, d->stream);
-    }
+    const Timed t = timed_begin(d, d->stream); // behind the table's copy: the kernel alone is timed
     hipError_t e = cvt ? ftar::launch_gather_cvt(A, cvt, scale, scatter, grid, d->stream)
                        : ftar::launch_gather(A, scatter, grid, d->stream);
     if (e != hipSuccess) return set_err(e, cvt ? "gather_cvt_kernel launch" : "gather_kernel launch");
-    if (d->profiling && e0 && e1) {
-        (void)hipEventRecord(e1, d->stream);
-        d->pending.push_back(Pending{e0, e1, tag});
-    }
+    timed_end(d, d->stream, t, tag);
     return 0;
 }
 
@@ -404,12 +410,8 @@ int fdev_gather_cvt(ftar_dev *d, void *packed, const fdev_gent *table, int n, in
 int fdev_run_bg(ftar_dev *d, int dtype, int op, const fdev_seg *segs, int nseg, int tag)
 {
     int rc = ensure_bg(d);
+    if (!rc) rc = order_after_main(d, d->bg);
     if (rc) return rc;
-    hipEvent_t e = get_event(d);
-    if (!e) return set_err(hipErrorOutOfMemory, "hipEventCreate");
-    HIPCHK(hipEventRecord(e, d->stream));
-    HIPCHK(hipStreamWaitEvent(d->bg, e, 0));
-    d->event_pool.push_back(e);
     return run_on(d, d->bg, dtype, op, segs, nseg, tag);
 }
 
@@ -420,12 +422,8 @@ int fdev_copy(ftar_dev *d, int bg, void *dst, const void *src, size_t bytes, int
     hipStream_t st = d->stream;
     if (bg) { // ordered after the main stream, like fdev_run_bg
         int rc = ensure_bg(d);
+        if (!rc) rc = order_after_main(d, d->bg);
         if (rc) return rc;
-        hipEvent_t e = get_event(d);
-        if (!e) return set_err(hipErrorOutOfMemory, "hipEventCreate");
-        HIPCHK(hipEventRecord(e, d->stream));
-        HIPCHK(hipStreamWaitEvent(d->bg, e, 0));
-        d->event_pool.push_back(e);
         st = d->bg;
     }
     if (remote) {
@@ -436,17 +434,9 @@ int fdev_copy(ftar_dev *d, int bg, void *dst, const void *src, size_t bytes, int
     }
     note_launch(d, st, ~0u, false, nullptr);
     if (d->trace) tr_launch(d, st, nullptr, tr_rw(d, {{src, bytes}}, {{dst, bytes}}), 0, "sdma");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (d->profiling) {
-        e0 = get_event(d);
-        e1 = get_event(d);
-        if (e0) (void)hipEventRecord(e0, st);
-    }
+    const Timed t = timed_begin(d, st);
     HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
-    if (d->profiling && e0 && e1) {
-        (void)hipEventRecord(e1, st);
-        d->pending.push_back(Pending{e0, e1, tag});
-    }
+    timed_end(d, st, t, tag);
     return 0;
 }
 
@@ -477,6 +467,21 @@ int fdev_user_host_waits(const ftar_dev *d) { return d->user_host_waits; }
 
 namespace fdevi {
 
+// Records the fenced marker of `st` (main or background): a release of everything queued on
+// it so far.  `*ev`, where given, is the event recorded, for a drain to wait on.
+static int release_marker(ftar_dev *d, hipStream_t st, hipEvent_t *ev = nullptr)
+{
+    hipEvent_t fence = st == d->bg ? d->fence_bg : d->fence_main;
+    if (d->tr_drop == 1) { // TEST-ONLY (FTAR_TRACE_DROP=release): the marker without its system fence
+        hipEvent_t &nf = st == d->bg ? d->nofence_bg : d->nofence_main;
+        if (!nf) HIPCHK(hipEventCreateWithFlags(&nf, hipEventDisableTiming | hipEventDisableSystemFence));
+        fence = nf;
+    }
+    HIPCHK(hipEventRecord(fence, st));
+    if (ev) *ev = fence;
+    return 0;
+}
+
 // Waits for everything enqueued on `st` by spinning on a fenced marker event.  Its
 // system-scope sequentially consistent fence is what makes a step's results visible to
 // the peers that pull them next -- the writeback puts this GPU's dirty L2 lines in HBM
@@ -487,22 +492,10 @@ namespace fdevi {
 // packet fences.
 int sync_stream(ftar_dev *d, hipStream_t st, int (*poll)(void *), void *arg)
 {
-    hipEvent_t fence = st == d->bg ? d->fence_bg : d->fence_main;
-    if (d->tr_drop == 1) { // TEST-ONLY (FTAR_TRACE_DROP=release): the drain without its system fence
-        hipEvent_t &nf = st == d->bg ? d->nofence_bg : d->nofence_main;
-        if (!nf) HIPCHK(hipEventCreateWithFlags(&nf, hipEventDisableTiming | hipEventDisableSystemFence));
-        fence = nf;
-    }
-    HIPCHK(hipEventRecord(fence, st));
-    for (;;) {
-        hipError_t e = hipEventQuery(fence);
-        if (e == hipSuccess) break;
-        if (e != hipErrorNotReady) return set_err(e, "hipEventQuery");
-        if (poll) {
-            int r = poll(arg);
-            if (r) return r;
-        }
-    }
+    hipEvent_t fence = nullptr;
+    int rc = release_marker(d, st, &fence);
+    if (!rc) rc = spin(fence, poll, arg);
+    if (rc) return rc;
     tr(d, "D %s %c", d->tr_drop == 1 ? "nf" : "mk", st == d->bg ? 'b' : 'm');
     return 0;
 }
@@ -528,6 +521,14 @@ int wait_signal(ftar_dev *d, unsigned tag, int (*poll)(void *), void *arg)
     }
 }
 
+// The end of a drain: the gated launches it covered are checked (verify_gate relaunches one
+// the device gave up) and the timings of the completed launches collected.
+static int after_drain(ftar_dev *d, int (*poll)(void *), void *arg)
+{
+    int rc = verify_gate(d, poll, arg);
+    return rc ? rc : harvest(d);
+}
+
 } // namespace fdevi
 
 extern "C" {
@@ -545,9 +546,7 @@ int fdev_sync(ftar_dev *d, int (*poll)(void *), void *arg)
         d->unsignalled = 1; // the gated launch, drained through a marker after its gate opens
         if (rc) return rc;
         tr(d, "D pre");
-        rc = verify_gate(d, poll, arg);
-        if (rc) return rc;
-        return harvest(d);
+        return after_drain(d, poll, arg);
     }
     if (d->gate_pending) {
         // a launch waits on its closed gate: drain what was queued before it (all of it
@@ -562,9 +561,7 @@ int fdev_sync(ftar_dev *d, int (*poll)(void *), void *arg)
         if (rc) return rc;
         // an earlier gated launch among them (RD: step s, opened; step s + 1 pending) has
         // completed too: check it now, before step s + 1 can read its result
-        rc = verify_gate(d, poll, arg);
-        if (rc) return rc;
-        return harvest(d);
+        return after_drain(d, poll, arg);
     }
     if (!d->unsignalled && !d->signalled && !d->force_fence) {
         rc = 0; // nothing queued since the last drain
@@ -580,9 +577,7 @@ int fdev_sync(ftar_dev *d, int (*poll)(void *), void *arg)
     }
     d->unsignalled = d->signalled = d->force_fence = 0;
     if (rc) return rc;
-    rc = verify_gate(d, poll, arg); // the gated launch has completed: did its gate time out?
-    if (rc) return rc;
-    return harvest(d);
+    return after_drain(d, poll, arg); // the gated launch has completed: did its gate time out?
 }
 
 void fdev_fence_next_drain(ftar_dev *d) { d->force_fence = 1; }
@@ -613,13 +608,8 @@ int fdev_peer_wait(ftar_dev *d, void *flag, void *const *peer_flags, int npeers,
     W.vval = d->pw_vval;
     W.ticks = d->gate_ticks;
     // release: everything this rank queued so far is in HBM, device-wide, before its flag
-    if (d->tr_drop == 1) { // TEST-ONLY (FTAR_TRACE_DROP=release): the flag without the release
-        if (!d->nofence_main)
-            HIPCHK(hipEventCreateWithFlags(&d->nofence_main, hipEventDisableTiming | hipEventDisableSystemFence));
-        HIPCHK(hipEventRecord(d->nofence_main, d->stream));
-    } else {
-        HIPCHK(hipEventRecord(d->fence_main, d->stream));
-    }
+    int rc = release_marker(d, d->stream);
+    if (rc) return rc;
     if (d->trace) {
         std::string own, peers;
         tr_fmt(d, {{flag, 8}}, own);
@@ -750,12 +740,8 @@ int fdev_d2h_async(ftar_dev *d, void *dst, const void *src, size_t bytes)
 {
     if (d->gate_pending) (void)fdev_gate_open(d, 1);
     int rc = ensure_pipe(d);
+    if (!rc) rc = order_after_main(d, d->d2h);
     if (rc) return rc;
-    hipEvent_t e = get_event(d);
-    if (!e) return set_err(hipErrorOutOfMemory, "hipEventCreate");
-    HIPCHK(hipEventRecord(e, d->stream));
-    HIPCHK(hipStreamWaitEvent(d->d2h, e, 0));
-    d->event_pool.push_back(e);
     HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, d->d2h));
     return 0;
 }

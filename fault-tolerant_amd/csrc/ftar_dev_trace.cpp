@@ -19,14 +19,20 @@ namespace fdevi {
 // their peer mappings).  `rel` = the kernel releases its stores at system scope before it signals
 // (signal_done), `acq` = it invalidates before its loads (signal_acquire), `fence` = a fenced marker
 // was queued right in front of it.  tests/fence_check.py checks the cross-rank rules on the lines.
-void tr(ftar_dev *d, const char *fmt, ...)
+static void trv(ftar_dev *d, const char *fmt, va_list ap)
 {
     if (!d->trace) return;
+    vfprintf(d->trace, fmt, ap);
+    fputc('\n', d->trace);
+}
+
+void tr(ftar_dev *d, const char *fmt, ...)
+{
+    if (!d->trace) return; // (the untraced path stops here)
     va_list ap;
     va_start(ap, fmt);
-    vfprintf(d->trace, fmt, ap);
+    trv(d, fmt, ap);
     va_end(ap);
-    fputc('\n', d->trace);
 }
 
 void tr_fmt(const ftar_dev *d, const std::vector<TrRange> &v, std::string &out)
@@ -148,12 +154,10 @@ void fdev_trace_external_write(ftar_dev *d, const void *p, size_t bytes)
 
 void fdev_trace_note(ftar_dev *d, const char *fmt, ...)
 {
-    if (!d->trace) return;
     va_list ap;
     va_start(ap, fmt);
-    vfprintf(d->trace, fmt, ap);
+    trv(d, fmt, ap);
     va_end(ap);
-    fputc('\n', d->trace);
 }
 
 } // extern "C"

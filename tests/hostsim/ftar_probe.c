@@ -18,7 +18,9 @@
  *      FTAR_PROBE_SLEEP_US=t (sleep before every call: a late rank, with FTAR_PROBE_RANK_ENV),
  *      FTAR_PROBE_CYCLE_SEQ=i,j,... (host-sim, with FTAR_PROBE_DEVICE=1: call k sends from
  *      exportable buffer number seq[k], each holding the input -- a caller cycling its send
- *      buffers through the peers' mapping caches)
+ *      buffers through the peers' mapping caches),
+ *      FTAR_PROBE_PROFILE=1 (ftar_set_profiling on: the status line's kernel count and
+ *      kernel time are those of the timed launches)
  */
 #include <dlfcn.h>
 #include <stdio.h>
@@ -79,6 +81,7 @@ int main(void)
     if (ftar_init(&comm) != FTAR_SUCCESS) return 3;
     int rank;
     ftar_world_rank(comm, &rank);
+    if (getenv("FTAR_PROBE_PROFILE") && atoi(getenv("FTAR_PROBE_PROFILE"))) ftar_set_profiling(comm, 1);
     size_t bytes = count * esize(dt);
     size_t pad = off * esize(dt);
     int pinned = getenv("FTAR_PROBE_PINNED") ? atoi(getenv("FTAR_PROBE_PINNED")) : 0;
@@ -141,10 +144,11 @@ int main(void)
         fclose(f);
         snprintf(path, sizeof(path), "%s/status_%d_%d.txt", dir, rank, it);
         f = fopen(path, "w");
-        fprintf(f, "%d %d %d %d %lld %lld %lld %d %d %d %d %d %d %d %d %d %d %d %d\n", rc, crank, csize, st.recoveries,
+        fprintf(f, "%d %d %d %d %lld %lld %lld %d %d %d %d %d %d %d %d %d %d %d %d %lld\n", rc, crank, csize, st.recoveries,
                 (long long)(st.wall_s * 1e6), (long long)(st.sync_wait_s * 1e6), (long long)(st.drain_s * 1e6), st.syncs,
                 st.relayed_steps, st.mesh_steps, st.gated_launches, st.gated_skips, st.step0_copy, st.gate_holds,
-                st.gate_relaunches, st.peer_waits, st.peer_wait_skips, st.steps, st.kernels);
+                st.gate_relaunches, st.peer_waits, st.peer_wait_skips, st.steps, st.kernels,
+                (long long)(st.kernel_ms * 1e6) /* ns */);
         fclose(f);
     }
     ftar_finalize(comm);

@@ -812,3 +812,47 @@ def test_device_knob_refused(oracle, name, value):
     r = H.run_probe("raben", ins, backend="gpu", devmap=ALL_ON_GPU0, timeout=120, env_extra={name: value})
     assert r.returncode != 0 and not r.outputs
     assert f"{name}={value} is not " in r.stderr and "refused" in r.stderr, r.stderr[-1500:]
+
+
+# ftar_last_stats().kernels of a profiled call, per world rank: what the library reported at
+# commit 81d0c59, the parent of the change that gave the five timed launch sites (segment, tree,
+# tree batch, gather, copy) one begin / end pair -- measured with this test's own job, three
+# jobs of three calls per case, every call of every job the same (profiles/launch_glue/README.md).
+# The drains are fenced markers (FTAR_FLAG_SYNC=0): a marker completes behind the stop events
+# queued before it, so every timed launch is harvested in its own call.  A drain on a kernel's
+# own flag can return before the launch's stop event has completed, which is then counted in the
+# next call: at the defaults the parent's counts varied from job to job (rd, 2 ranks: 2 1 1 and
+# 1 2 2 on the same rank).
+F0 = {"FTAR_FLAG_SYNC": "0"}
+PROFILED_KERNELS = [
+    ("rd", 2, F0, (2, 2)),
+    ("rd", 4, F0, (3, 3, 3, 3)),
+    ("raben", 2, F0, (2, 2)),
+    ("raben", 4, F0, (2, 2, 2, 2)),
+    # 2 ranks and a spare, the step-0 redundancy copy kept: timed on the background stream, as a
+    # segment launch and (FTAR_COPY_ENGINE) as a copy followed by one
+    ("raben", 3, dict(F0, FTAR_REDUNDANCY="1"), (6, 3, 4)),
+    ("raben", 3, dict(F0, FTAR_REDUNDANCY="1", FTAR_COPY_ENGINE="1"), (8, 3, 6)),
+]
+
+
+@pytest.mark.parametrize("algo,p,env,want", PROFILED_KERNELS,
+                         ids=[f"{a}-p{p}" + ("-spare" if "FTAR_REDUNDANCY" in e else "") +
+                              ("-sdma" if "FTAR_COPY_ENGINE" in e else "") for a, p, e, _ in PROFILED_KERNELS])
+def test_profiled_launch_counts(oracle, algo, p, env, want):
+    """Profiling on (which disables gating), 1024 float32: every call reports the parent's
+    number of timed launches and a device time above zero, on every rank; results bit-exact."""
+    ins = oracle.random_inputs(p, 1024, seed=p)
+    o = (oracle.rabenseifner if algo == "raben" else oracle.recursive_doubling)(ins)
+    r = H.run_probe(algo, ins, iters=3, backend="gpu", devmap=ALL_ON_GPU0, timeout=100,
+                    env_extra=dict(env, FTAR_PROBE_PROFILE="1"))
+    assert r.returncode == 0 and not r.aborted, r.stderr[-2000:]
+    for w in range(p):
+        for it in range(3):
+            st = r.status[w][it]
+            print(f"rank {w} call {it}: kernels {st[18]} kernel_ns {st[19]} step0_copy {st[12]}")
+            assert st[0] == 0, (w, it, st)
+            assert np.array_equal(r.outputs[w][it].view(np.uint32), o.outputs[w].view(np.uint32)), (w, it)
+            assert st[18] == want[w], (w, it, st[18], want)
+            assert st[19] > 0, (w, it, st)
+            assert st[12] == (1 if "FTAR_REDUNDANCY" in env else 0), (w, it, st)
