@@ -121,6 +121,7 @@ def lib():
         "ftar_recursive_doubling_host": ([vp, vp, sz, i, i, vp], i),
         "ftar_allreduce_multi": ([i, pp, pp, ctypes.POINTER(sz), i, i, i, vp], i),
         "ftar_allreduce_multi_acc32": ([i, pp, pp, ctypes.POINTER(sz), i, i, i, ctypes.c_float, vp], i),
+        "ftar_allreduce_multi_mixed": ([i, pp, pp, ctypes.POINTER(sz), ctypes.POINTER(i), i, i, ctypes.c_float, vp], i),
         "ftar_reduce_local": ([vp, vp, sz, i, i, vp], i),
         "ftar_set_reduce_variant": ([i], i),
         "ftar_comm_set_stream": ([vp, vp], i),
@@ -398,6 +399,37 @@ class Comm:
         rb = (vp * n)(*[_ptr(o) if o.numel() else None for o in outs])
         return lib().ftar_allreduce_multi_acc32(algo, sb, rb, (sz * n)(*[t.numel() for t in tensors]), n,
                                                 _dtype_of(tensors[0]), op, float(scale), self._h)
+
+    def allreduce_multi_mixed(self, tensors, out=None, op: int = SUM, algo="raben", scale: float = 1.0) -> int:
+        """allreduce_multi_acc32 for a list of contiguous tensors of any mix of torch.float16,
+        torch.bfloat16 and torch.float32 (a model's whole gradient list in one call): every
+        element is widened to float32 (a float32 entry copied), the float32 schedule `algo` runs
+        on the dense concatenation, and out[i] (None: in place; the dtype and numel of tensor i)
+        receives scale * result -- as it is for a float32 entry, rounded once to nearest even for
+        a 2-byte one.  The scale is the caller's; it is applied whatever the op."""
+        import torch
+        outs = tensors if out is None else out
+        if len(outs) != len(tensors):
+            raise FtarError("allreduce_multi_mixed: as many outputs as inputs")
+        if not 1 <= len(tensors) <= MULTI_MAX:
+            raise FtarError(f"allreduce_multi_mixed: 1 .. {MULTI_MAX} tensors")
+        algo = {"raben": ALGO_RABENSEIFNER, "rd": ALGO_RD}.get(algo, algo)
+        if algo not in (ALGO_RD, ALGO_RABENSEIFNER):
+            raise FtarError(f"allreduce_multi_mixed: unknown algo {algo!r}")
+        for t, o in zip(tensors, outs):
+            if t.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+                raise FtarError(f"allreduce_multi_mixed: float16, bfloat16 or float32 tensors, not {t.dtype}")
+            if o.dtype != t.dtype:
+                raise FtarError("allreduce_multi_mixed: an output's dtype differs from its input's")
+            if o.numel() != t.numel():
+                raise FtarError("allreduce_multi_mixed: an output's size differs from its input's")
+        n = len(tensors)
+        vp, sz = ctypes.c_void_p, ctypes.c_size_t
+        sb = (vp * n)(*[_ptr(t) if t.numel() else None for t in tensors])
+        rb = (vp * n)(*[_ptr(o) if o.numel() else None for o in outs])
+        return lib().ftar_allreduce_multi_mixed(algo, sb, rb, (sz * n)(*[t.numel() for t in tensors]),
+                                                (ctypes.c_int * n)(*[_dtype_of(t) for t in tensors]), n, op,
+                                                float(scale), self._h)
 
     def finalize(self):
         if self._h:

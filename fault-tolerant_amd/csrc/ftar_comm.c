@@ -1177,18 +1177,20 @@ int ftar_set_profiling(ftar_comm *c, int on)
 
 /* The gather (scatter = 0: entries -> packed) or scatter launch: the device layer's table-driven
  * kernel -- the converting one for `cvt`, the 2-byte float type of the user buffers (0 = the plain
- * mover) -- or where it has no plain one (host-sim) FDEV_COPY segments in groups of FDEV_MAX_SEGS. */
+ * mover), the mixed one for `mix`, the entries' own types -- or where it has no plain one
+ * (host-sim) FDEV_COPY segments in groups of FDEV_MAX_SEGS. */
 static void multi_move(ftar_comm *c, void *packed, const fdev_gent *tab, int n, int dtype, int op, int cvt,
-                       float scale, int scatter)
+                       const int *mix, float scale, int scatter)
 {
     /* nothing to return: a launch that fails ends the job in either path (ftar_launch_check, which
      * ftar_run goes through as well, calls ftar_ctrl_abort) -- a rank never goes on to the
      * schedule with a vector gathered in part */
     const size_t es = ftar_esize(dtype);
-    if (cvt || fdev_gather) {
+    if (mix || cvt || fdev_gather) {
         ftar_note_launch(c, NULL, 0);
-        ftar_launch_check(c, cvt ? fdev_gather_cvt(c->dev, packed, tab, n, cvt, scale, scatter, FDEV_TAG_LOCAL)
-                                 : fdev_gather(c->dev, packed, tab, n, es, scatter, FDEV_TAG_LOCAL));
+        ftar_launch_check(c, mix   ? fdev_gather_mix(c->dev, packed, tab, mix, n, scale, scatter, FDEV_TAG_LOCAL)
+                             : cvt ? fdev_gather_cvt(c->dev, packed, tab, n, cvt, scale, scatter, FDEV_TAG_LOCAL)
+                                   : fdev_gather(c->dev, packed, tab, n, es, scatter, FDEV_TAG_LOCAL));
         return;
     }
     for (int i = 0; i < n; i += FDEV_MAX_SEGS) {
@@ -1234,13 +1236,17 @@ static int multi_plain(ftar_algo algo, const void *s, void *r, size_t n, ftar_dt
  * dense vector, so block boundaries, operand order, recovery and kill points are the plain
  * call's; every input is read (the gather is queued first on the rank's stream) before any
  * output is written (the scatter is queued after the schedule has drained).
- * Both list entry points run it.  A user element has `ues` bytes, a packed one `pes` (the
+ * All three list entry points run it.  A user element has `ues` bytes, a packed one `pes` (the
  * tables count packed bytes); the schedule runs on `sched`.  ftar_allreduce_multi: ues = pes,
  * sched the caller's dtype, the plain mover.  ftar_allreduce_multi_acc32: float32 staging for
  * lists of 2-byte floats (ues 2, pes 4, sched FLOAT32) -- the gather widens into hsend (`cvt` =
- * the caller's dtype, fdev_gather_cvt), the scatter stores scale * hrecv[j] rounded once. */
+ * the caller's dtype, fdev_gather_cvt), the scatter stores scale * hrecv[j] rounded once.
+ * ftar_allreduce_multi_mixed: the same staging with `ues` and the conversion per entry -- `mix`
+ * holds every entry's own type (float16, bfloat16, float32: ues 2, 2, 4), `ues` and `cvt` are
+ * not looked at, the mover is fdev_gather_mix and no list goes straight through. */
 static int multi_core(ftar_algo algo, const void *const *sbufs, void *const *rbufs, const size_t *counts, int nbufs,
-                      size_t ues, size_t pes, ftar_dtype sched, int cvt, float scale, ftar_op op, ftar_comm *c)
+                      const ftar_dtype *mix, size_t ues, size_t pes, ftar_dtype sched, int cvt, float scale, ftar_op op,
+                      ftar_comm *c)
 {
     if (!sbufs || !rbufs || !counts || nbufs < 1 || nbufs > FTAR_MULTI_MAX ||
         (algo != FTAR_ALGO_RD && algo != FTAR_ALGO_RABENSEIFNER))
@@ -1248,26 +1254,33 @@ static int multi_core(ftar_algo algo, const void *const *sbufs, void *const *rbu
     /* the two tables (24 KiB each at FTAR_MULTI_MAX); `in` first holds the outputs sorted by
      * address, for the overlap check */
     fdev_gent in[FTAR_MULTI_MAX], out[FTAR_MULTI_MAX];
+    int ty[FTAR_MULTI_MAX]; /* the non-empty entries' types (mix) */
     size_t total = 0;
     int n = 0, only = -1;
     for (int i = 0; i < nbufs; i++) {
         if (counts[i] == 0) continue;
         if (counts[i] > (size_t)INT64_MAX / 16 - total || !sbufs[i] || !rbufs[i]) return FTAR_ERR_ARG;
-        if (cvt && (((uintptr_t)sbufs[i] | (uintptr_t)rbufs[i]) & 1)) return FTAR_ERR_ARG;
+        if (mix) {
+            if (mix[i] != FTAR_FLOAT16 && mix[i] != FTAR_BFLOAT16 && mix[i] != FTAR_FLOAT32) return FTAR_ERR_ARG;
+            ues = ftar_esize(mix[i]);
+            ty[n] = (int)mix[i];
+        }
+        /* (a 2-byte or float32 entry of a converting call needs its own element's alignment) */
+        if ((mix || cvt) && (((uintptr_t)sbufs[i] | (uintptr_t)rbufs[i]) & (ues - 1))) return FTAR_ERR_ARG;
         const size_t b = counts[i] * ues;
         if (fdev_check_ptr(c->dev, sbufs[i], b) || fdev_check_ptr(c->dev, rbufs[i], b)) return FTAR_ERR_ARG;
         out[n] = (fdev_gent){rbufs[i], total * pes, counts[i] * pes};
+        in[n] = (fdev_gent){rbufs[i], 0, b}; /* the user range */
         total += counts[i];
         only = i;
         n++;
     }
-    memcpy(in, out, sizeof(fdev_gent) * (size_t)n);
     qsort(in, (size_t)n, sizeof(fdev_gent), by_ptr);
     for (int i = 1; i < n; i++) /* on the user ranges */
-        if ((uintptr_t)in[i - 1].ptr + in[i - 1].bytes / pes * ues > (uintptr_t)in[i].ptr) return FTAR_ERR_ARG;
+        if ((uintptr_t)in[i - 1].ptr + in[i - 1].bytes > (uintptr_t)in[i].ptr) return FTAR_ERR_ARG;
     if (n == 0) return multi_plain(algo, NULL, NULL, 0, sched, op, c);
     /* one buffer goes straight through, unless it is to be converted like any other */
-    if (n == 1 && !cvt) return multi_plain(algo, sbufs[only], rbufs[only], counts[only], sched, op, c);
+    if (n == 1 && !cvt && !mix) return multi_plain(algo, sbufs[only], rbufs[only], counts[only], sched, op, c);
     for (int i = 0, k = 0; i < nbufs; i++)
         if (counts[i]) {
             in[k] = (fdev_gent){(void *)(uintptr_t)sbufs[i], out[k].off, out[k].bytes};
@@ -1278,13 +1291,13 @@ static int multi_core(ftar_algo algo, const void *const *sbufs, void *const *rbu
     ftar_stats_begin(c); /* the call's one record and call index; the schedule continues it (chunk_cont) */
     c->stats.coalesced = n;
     fdev_order_after(c->dev, c->user_stream); /* the inputs may still be in flight on the caller's stream */
-    multi_move(c, c->hsend, in, n, (int)sched, (int)op, cvt, 1.0f, 0);
+    multi_move(c, c->hsend, in, n, (int)sched, (int)op, cvt, mix ? ty : NULL, 1.0f, 0);
     multi_fold(c);
     c->chunk_cont = 1;
     int rc = multi_plain(algo, c->hsend, c->hrecv, total, sched, op, c);
     c->chunk_cont = 0;
     if (rc) return rc;
-    multi_move(c, c->hrecv, out, n, (int)sched, (int)op, cvt, scale, 1);
+    multi_move(c, c->hrecv, out, n, (int)sched, (int)op, cvt, mix ? ty : NULL, scale, 1);
     ftar_drain(c); /* blocking: the results are in the caller's buffers */
     multi_fold(c);
     c->stats.wall_s = now_s() - c->t0;
@@ -1298,7 +1311,7 @@ int ftar_allreduce_multi(ftar_algo algo, const void *const *sbufs, void *const *
     int rc = ftar_check_op((int)dtype, (int)op);
     if (rc) return rc;
     const size_t es = ftar_esize(dtype);
-    return multi_core(algo, sbufs, rbufs, counts, nbufs, es, es, dtype, 0, 1.0f, op, c);
+    return multi_core(algo, sbufs, rbufs, counts, nbufs, NULL, es, es, dtype, 0, 1.0f, op, c);
 }
 
 int ftar_allreduce_multi_acc32(ftar_algo algo, const void *const *sbufs, void *const *rbufs, const size_t *counts,
@@ -1309,7 +1322,18 @@ int ftar_allreduce_multi_acc32(ftar_algo algo, const void *const *sbufs, void *c
     if (rc) return rc;
     /* (a build without the converting mover, host-sim, refuses the call) */
     if ((dtype != FTAR_FLOAT16 && dtype != FTAR_BFLOAT16) || !fdev_gather_cvt || !isfinite(scale)) return FTAR_ERR_ARG;
-    return multi_core(algo, sbufs, rbufs, counts, nbufs, 2, 4, FTAR_FLOAT32, (int)dtype, scale, op, c);
+    return multi_core(algo, sbufs, rbufs, counts, nbufs, NULL, 2, 4, FTAR_FLOAT32, (int)dtype, scale, op, c);
+}
+
+int ftar_allreduce_multi_mixed(ftar_algo algo, const void *const *sbufs, void *const *rbufs, const size_t *counts,
+                               const ftar_dtype *dtypes, int nbufs, ftar_op op, float scale, ftar_comm *c)
+{
+    if (!c) return FTAR_ERR_ARG;
+    int rc = ftar_check_op((int)FTAR_FLOAT32, (int)op); /* the three types share float32's op set */
+    if (rc) return rc;
+    /* (a build without the mixed mover, host-sim, refuses the call) */
+    if (!dtypes || !fdev_gather_mix || !isfinite(scale)) return FTAR_ERR_ARG;
+    return multi_core(algo, sbufs, rbufs, counts, nbufs, dtypes, 0, 4, FTAR_FLOAT32, 0, scale, op, c);
 }
 
 /* ---- local reduce --------------------------------------------------------- */

@@ -120,6 +120,13 @@ int fdev_gather(ftar_dev *d, void *packed, const fdev_gent *table, int n, size_t
  * (fdev_has_dtype), so the shared host C has nothing to fall back to and refuses the call. */
 int fdev_gather_cvt(ftar_dev *d, void *packed, const fdev_gent *table, int n, int dtype, float scale, int scatter,
                     int tag) __attribute__((weak));
+/* The mixed mover of ftar_allreduce_multi_mixed: the same launch once more, entry i's user buffer
+ * of type dtypes[i] (1: float32, 16, 17), aligned to its element.  The table counts PACKED bytes
+ * as fdev_gather_cvt's; a float32 entry is copied on gather and stores scale * packed[j] on
+ * scatter, a 2-byte entry moves as fdev_gather_cvt moves it.  One launch whatever the mix.  Weak
+ * as well: the host-sim layer does not define it and the shared host C refuses the call. */
+int fdev_gather_mix(ftar_dev *d, void *packed, const fdev_gent *table, const int *dtypes, int n, float scale,
+                    int scatter, int tag) __attribute__((weak));
 /* Tree reduce of nsrc (2, 4, 8 or 16) sources into out on the rank's stream:
  * out[i] = ((src0 op src1) op (src2 op src3)) op ...; bit j of remote_mask marks src[j]
  * as a peer mapping (byte accounting). */

@@ -326,8 +326,13 @@ extern "C" {
 // before it returns, so no copy is in flight under a rewrite.
 // `cvt` = 0: the plain mover.  Otherwise the 2-byte float type of the user buffers of the
 // converting mover: esize = 4, the table in packed bytes, the user side half as many.
+// `mix` (with cvt = 0, esize = 4): the mixed mover, entry i's user buffer of type mix[i] -- the
+// types travel behind the table's n entries in the same mirror and device buffer (ftar::mix_types),
+// so each half has room for gt_cap entries and as many 32-bit words, and one copy uploads both.
+static size_t mix_user_bytes(size_t packed_bytes, int dtype) { return dtype == ftar::kFloat32 ? packed_bytes : packed_bytes / 2; }
+
 static int gather_launch(ftar_dev *d, void *packed, const fdev_gent *table, int n, size_t esize, int cvt, float scale,
-                         int scatter, int tag)
+                         int scatter, int tag, const int *mix = nullptr)
 {
     if (!packed || !table || n < 1 || n > ftar::kMaxGather || tag < 0 || tag >= FDEV_NTAGS ||
         !(esize == 1 || esize == 2 || esize == 4 || esize == 8 || esize == 16)) {
@@ -350,12 +355,18 @@ static int gather_launch(ftar_dev *d, void *packed, const fdev_gent *table, int 
         if (d->gt_host) (void)hipHostFree(d->gt_host);
         d->gt_dev = d->gt_host = nullptr;
         d->gt_cap = 0;
-        HIPCHK(hipMalloc((void **)&d->gt_dev, 2 * (size_t)cap * sizeof(ftar::GEntry)));
-        HIPCHK(hipHostMalloc((void **)&d->gt_host, 2 * (size_t)cap * sizeof(ftar::GEntry), hipHostMallocDefault));
+        HIPCHK(hipMalloc((void **)&d->gt_dev, 2 * (size_t)cap * ftar::kMixEntryBytes));
+        HIPCHK(hipHostMalloc((void **)&d->gt_host, 2 * (size_t)cap * ftar::kMixEntryBytes, hipHostMallocDefault));
         d->gt_cap = cap;
     }
-    ftar::GEntry *hm = d->gt_host + (scatter ? d->gt_cap : 0), *dm = d->gt_dev + (scatter ? d->gt_cap : 0);
+    // (a half is gt_cap * 28 bytes, gt_cap a multiple of 64: 8-byte aligned)
+    const size_t half = scatter ? (size_t)d->gt_cap * ftar::kMixEntryBytes : 0;
+    ftar::GEntry *hm = (ftar::GEntry *)((char *)d->gt_host + half), *dm = (ftar::GEntry *)((char *)d->gt_dev + half);
     for (int i = 0; i < n; i++) hm[i] = ftar::GEntry{table[i].ptr, table[i].off, table[i].bytes};
+    if (mix) {
+        unsigned *ty = const_cast<unsigned *>(ftar::mix_types(hm, n));
+        for (int i = 0; i < n; i++) ty[i] = (unsigned)mix[i];
+    }
     ftar::GatherArgs A{};
     A.packed = (char *)packed;
     A.tab = dm;
@@ -369,20 +380,27 @@ static int gather_launch(ftar_dev *d, void *packed, const fdev_gent *table, int 
     }
     A.ntiles = (unsigned)tiles;
     const unsigned grid = A.ntiles < d->max_blocks ? A.ntiles : d->max_blocks;
-    d->ctr.hbm_bytes += (cvt ? 1.5 : 2.0) * (double)total; // (converting: 2 + 4 bytes per element)
+    if (mix) { // 4 bytes plus the entry's own element size
+        for (int i = 0; i < n; i++) d->ctr.hbm_bytes += (double)(table[i].bytes + mix_user_bytes(table[i].bytes, mix[i]));
+    } else {
+        d->ctr.hbm_bytes += (cvt ? 1.5 : 2.0) * (double)total; // (converting: 2 + 4 bytes per element)
+    }
     note_launch(d, d->stream, grid, true, &A.sig);
     if (d->trace) {
         std::vector<TrRange> user, pk;
-        for (int i = 0; i < n; i++) user.push_back({table[i].ptr, cvt ? table[i].bytes / 2 : table[i].bytes});
+        for (int i = 0; i < n; i++)
+            user.push_back({table[i].ptr, mix ? mix_user_bytes(table[i].bytes, mix[i]) : cvt ? table[i].bytes / 2 : table[i].bytes});
         pk.push_back({packed, total});
         tr_launch(d, d->stream, &A.sig, scatter ? tr_rw(d, pk, user) : tr_rw(d, user, pk), 0, "k");
     }
     // (behind note_launch: a fenced marker it queued stays in front of everything of this launch)
-    HIPCHK(hipMemcpyAsync(dm, hm, (size_t)n * sizeof(ftar::GEntry), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(dm, hm, (size_t)n * (mix ? ftar::kMixEntryBytes : sizeof(ftar::GEntry)), hipMemcpyHostToDevice,
+                          d->stream));
     const Timed t = timed_begin(d, d->stream); // behind the table's copy: the kernel alone is timed
-    hipError_t e = cvt ? ftar::launch_gather_cvt(A, cvt, scale, scatter, grid, d->stream)
-                       : ftar::launch_gather(A, scatter, grid, d->stream);
-    if (e != hipSuccess) return set_err(e, cvt ? "gather_cvt_kernel launch" : "gather_kernel launch");
+    hipError_t e = mix   ? ftar::launch_gather_mix(A, ftar::mix_types(dm, n), scale, scatter, grid, d->stream)
+                   : cvt ? ftar::launch_gather_cvt(A, cvt, scale, scatter, grid, d->stream)
+                         : ftar::launch_gather(A, scatter, grid, d->stream);
+    if (e != hipSuccess) return set_err(e, mix ? "gather_mix_kernel launch" : cvt ? "gather_cvt_kernel launch" : "gather_kernel launch");
     timed_end(d, d->stream, t, tag);
     return 0;
 }
@@ -405,6 +423,27 @@ int fdev_gather_cvt(ftar_dev *d, void *packed, const fdev_gent *table, int n, in
             return 13;
         }
     return gather_launch(d, packed, table, n, 4, dtype, scale, scatter, tag);
+}
+
+int fdev_gather_mix(ftar_dev *d, void *packed, const fdev_gent *table, const int *dtypes, int n, float scale,
+                    int scatter, int tag)
+{
+    for (int i = 0; table && dtypes && i < n; i++) {
+        const int dt = dtypes[i];
+        if (dt != ftar::kFloat16 && dt != ftar::kBFloat16 && dt != ftar::kFloat32) {
+            snprintf(g_err, sizeof(g_err), "fdev_gather_mix: entry %d is not float16, bfloat16 or float32", i);
+            return 13;
+        }
+        if ((uintptr_t)table[i].ptr & (dt == ftar::kFloat32 ? 3 : 1)) {
+            snprintf(g_err, sizeof(g_err), "fdev_gather_mix: entry %d is not aligned to its element", i);
+            return 13;
+        }
+    }
+    if (!dtypes) {
+        snprintf(g_err, sizeof(g_err), "fdev_gather_mix: bad arguments");
+        return 13;
+    }
+    return gather_launch(d, packed, table, n, 4, 0, scale, scatter, tag, dtypes);
 }
 
 int fdev_run_bg(ftar_dev *d, int dtype, int op, const fdev_seg *segs, int nseg, int tag)

@@ -359,6 +359,21 @@ __host__ __device__ inline bool cvt_piece(const GEntry &E, size_t lo, size_t hi,
 // rounded once to nearest even into the 2-byte type); the gather widens exactly.
 hipError_t launch_gather_cvt(const GatherArgs &A, int dtype, float scale, int scatter, unsigned grid, hipStream_t s);
 
+// The mixed sibling (fdev_gather_mix: the mover of ftar_allreduce_multi_mixed).  The packed vector
+// is float32 and the table counts packed bytes, as the converting mover's; every entry has a type
+// of its own, kFloat16, kBFloat16 or kFloat32.  The types are a parallel array of n 32-bit words
+// that follows the n GEntry of the table in the same device buffer (and in the pinned mirror, so
+// one copy uploads both): GEntry, the other two kernels and their launches stay as they are, and
+// an entry still is three 8-byte scalar loads, its type one 4-byte load more.  A 2-byte entry
+// moves by cvt_piece / the converting mover's groups; a float32 entry by gather_piece with es = 4
+// (a copy on gather; on scatter scale * a, the same 16-byte accesses where user and packed
+// addresses are congruent mod 16).
+inline const unsigned *mix_types(const GEntry *tab, int n) { return (const unsigned *)(tab + n); }
+constexpr size_t kMixEntryBytes = sizeof(GEntry) + sizeof(unsigned);
+// types: device memory, mix_types(A.tab, A.n).  scale: applied on scatter only.
+hipError_t launch_gather_mix(const GatherArgs &A, const unsigned *types, float scale, int scatter, unsigned grid,
+                             hipStream_t s);
+
 unsigned plan_segments(const SegIn *in, int nin, size_t esize, unsigned max_blocks, KSegList *L);
 hipError_t launch_segments(int dtype, int op, const KSegList &L, unsigned grid, hipStream_t s);
 hipError_t launch_reduce_lds(int dtype, int op, void *inout, const void *in, size_t nvec, unsigned grid,

@@ -1162,6 +1162,103 @@ hipError_t launch_gather_cvt(const GatherArgs &A, int dtype, float scale, int sc
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------
+// mixed gather / scatter: every entry float16, bfloat16 or float32 <-> packed float32
+// ---------------------------------------------------------------------------------
+// A float32 entry's scatter: user[j] = scale * packed[j], one v_mul_f32 / v_pk_mul_f32 per
+// element and nothing beside it (a store follows, so there is no conversion to fold it into: -0
+// and subnormal products stay what IEEE says).  GPiece with es = 4: heads, tails and pieces that
+// are not congruent mod 16 go word by word (unit = 4 always: user pointers are 4-byte aligned,
+// packed offsets multiples of 4), the rest in 16-byte accesses; user side non-temporal, packed
+// side plain, kUnroll loads in flight per lane, as move_piece.
+__device__ __forceinline__ void scale_words(char *user, char *packed, size_t bytes, float scale, unsigned tid,
+                                            unsigned nth)
+{
+    FTAR_GLOBAL float *u = (FTAR_GLOBAL float *)user, *k = (FTAR_GLOBAL float *)packed;
+    const size_t n = bytes / 4;
+    for (size_t i = tid; i < n; i += nth) __builtin_nontemporal_store(scale * k[i], u + i);
+}
+
+__device__ __forceinline__ void scale_piece(const GPiece &P, char *packed, float scale, unsigned tid, unsigned nth)
+{
+    char *k = packed + P.poff;
+    scale_words(P.user, k, P.head, scale, tid, nth);
+    if (!P.vec) return;
+    FTAR_GLOBAL v4f *U = (FTAR_GLOBAL v4f *)(P.user + P.head), *K = (FTAR_GLOBAL v4f *)(k + P.head);
+    size_t i = tid;
+    for (; i + (size_t)(kUnroll - 1) * nth < P.nvec; i += (size_t)kUnroll * nth) {
+        v4f v[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; u++) v[u] = K[i + (size_t)u * nth];
+#pragma unroll
+        for (int u = 0; u < kUnroll; u++) __builtin_nontemporal_store(v[u] * scale, U + i + (size_t)u * nth);
+    }
+    for (; i < P.nvec; i += nth) __builtin_nontemporal_store(K[i] * scale, U + i);
+    const size_t done = P.head + P.nvec * 16;
+    scale_words(P.user + done, k + done, P.bytes - done, scale, tid, nth);
+}
+
+// gather_kernel's grid, search and walk.  The entry's type is one more scalar load (the array
+// behind the table, through the constant address space as well) and wave-uniform, so the choice
+// of the mover is a uniform branch; the waves of a workgroup may be on small entries of
+// different types at the same time.
+template <bool SCATTER>
+__global__ __launch_bounds__(kBlock) void gather_mix_kernel(GatherArgs A, const unsigned *types, float scale)
+{
+    signal_acquire(A.sig);
+    const unsigned b0 = (unsigned)__builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    const unsigned nb = (unsigned)__builtin_amdgcn_readfirstlane((int)gridDim.x);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned lane = threadIdx.x & 63;
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) GEntry *CTab; // scalar loads, as gather_kernel's
+    typedef const __attribute__((address_space(4))) unsigned *CTy;
+#else
+    typedef const GEntry *CTab;
+    typedef const unsigned *CTy;
+#endif
+    const CTab tab = (CTab)A.tab;
+    const CTy ty = (CTy)types;
+    for (unsigned t = b0; t < A.ntiles; t += nb) {
+        const size_t lo = (size_t)t * kTileBytes;
+        const size_t hi = lo + kTileBytes < A.total ? lo + kTileBytes : A.total;
+        for (int e = __builtin_amdgcn_readfirstlane(gather_first(tab, A.n, lo)); e < A.n; e++) {
+            const GEntry E = {tab[e].ptr, tab[e].off, tab[e].bytes};
+            const size_t pb = E.off > lo ? E.off : lo, pe = E.off + E.bytes < hi ? E.off + E.bytes : hi;
+            if (pb >= pe) break;
+            const bool big = pe - pb >= kWavePiece; // the workgroup's piece, or one wave's
+            if (big || (e & 3) == wave) {
+                const unsigned dt = (unsigned)__builtin_amdgcn_readfirstlane((int)ty[e]);
+                const unsigned tid = big ? threadIdx.x : lane, nth = big ? kBlock : 64;
+                if (dt == (unsigned)kFloat32) {
+                    GPiece P;
+                    gather_piece(E, lo, hi, A.packed, 4, &P);
+                    if (SCATTER) scale_piece(P, A.packed, scale, tid, nth);
+                    else move_piece<false>(P, A.packed, tid, nth);
+                } else {
+                    CPiece P;
+                    cvt_piece(E, lo, hi, A.packed, &P);
+                    if (dt == (unsigned)kFloat16) cvt_move_piece<f16_t, SCATTER>(P, A.packed, scale, tid, nth);
+                    else cvt_move_piece<bf16_t, SCATTER>(P, A.packed, scale, tid, nth);
+                }
+            }
+            if (E.off + E.bytes >= hi) break;
+        }
+    }
+    signal_done(A.sig);
+}
+
+hipError_t launch_gather_mix(const GatherArgs &A, const unsigned *types, float scale, int scatter, unsigned grid,
+                             hipStream_t s)
+{
+    if (!A.packed || !A.tab || !types || A.n < 1 || A.n > kMaxGather || grid == 0 || grid > A.ntiles || A.es != 4 ||
+        A.total % 4 || (size_t)A.ntiles != (A.total + kTileBytes - 1) / kTileBytes)
+        return hipErrorInvalidValue;
+    if (scatter) hipLaunchKernelGGL(gather_mix_kernel<true>, dim3(grid), dim3(kBlock), 0, s, A, types, scale);
+    else hipLaunchKernelGGL(gather_mix_kernel<false>, dim3(grid), dim3(kBlock), 0, s, A, types, scale);
+    return hipGetLastError();
+}
+
 hipError_t launch_segments(int dtype, int op, const KSegList &L, unsigned grid, hipStream_t s)
 {
     return with_type(dtype, op, [&](auto t) {

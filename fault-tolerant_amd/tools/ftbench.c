@@ -20,6 +20,9 @@
  * every call is one ftar_allreduce_multi over the list; the check and the output line are unchanged.
  * FTBENCH_ACC32=1 (with FTBENCH_MULTI and a 16-bit type): the call is ftar_allreduce_multi_acc32 with
  * scale 1 instead -- float32 accumulation; the sums are exact either way, so the check is the same.
+ * FTBENCH_MIXED=1 (with FTBENCH_MULTI; no element type, or f32): buffer k is bfloat16, float32, float16 for
+ * k mod 3 = 0, 1, 2 and the call is ftar_allreduce_multi_mixed with scale 1; the inputs are the 16-bit job's
+ * small integers, exact in all three types, so the check and the output line are the same again.
  *
  * Every rank hipMallocs float32 send / receive vectors of `count` elements on its device,
  * fills the send vector with its original rank (the reference drivers' input,
@@ -85,6 +88,8 @@ static float from_f16(uint16_t h)
 /* the 16-bit job: same schedule calls, same JSON line */
 static int run16(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev,
                  int multi, int acc32);
+/* the mixed-list job: ftar_allreduce_multi_mixed over bfloat16, float32 and float16 buffers in turn */
+static int runmixed(int rd, size_t count, int calls, ftar_comm *comm, int wrank, int wsize, int dev, int multi);
 /* the pair-type job (MAXLOC) */
 static int runpair(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm, int wrank, int wsize, int dev);
 /* the job on the 8-, 16-bit and unsigned integers (SUM, checked modulo 2^w) */
@@ -140,6 +145,14 @@ int main(int argc, char **argv)
     if (acc32 && !(multi && dt16)) {
         fprintf(stderr, "ftbench: FTBENCH_ACC32 needs FTBENCH_MULTI and f16 or bf16\n");
         return 2;
+    }
+    const char *xe = getenv("FTBENCH_MIXED");
+    if (xe && atoi(xe) != 0) {
+        if (!multi || dt16 || acc32) {
+            fprintf(stderr, "ftbench: FTBENCH_MIXED needs FTBENCH_MULTI, no element type (or f32) and no FTBENCH_ACC32\n");
+            return 2;
+        }
+        return runmixed(rd, count, calls, comm, wrank, wsize, dev, multi);
     }
     if (dt16) return run16(rd, count, calls, (ftar_dtype)dt16, comm, wrank, wsize, dev, multi, acc32);
     if (dtpair) return runpair(rd, count, calls, (ftar_dtype)dtpair, comm, wrank, wsize, dev);
@@ -323,6 +336,98 @@ static int run16(int rd, size_t count, int calls, ftar_dtype dt, ftar_comm *comm
     }
     (void)hipFree(s);
     (void)hipFree(r);
+    free(h);
+    return 0;
+}
+
+static const ftar_dtype mixed_cycle[3] = {FTAR_BFLOAT16, FTAR_FLOAT32, FTAR_FLOAT16};
+
+/* element i of a buffer of type dt */
+static void mixed_put(void *buf, ftar_dtype dt, size_t i, float v)
+{
+    if (dt == FTAR_FLOAT32) ((float *)buf)[i] = v;
+    else ((uint16_t *)buf)[i] = dt == FTAR_BFLOAT16 ? to_bf16(v) : to_f16(v);
+}
+static float mixed_get(const void *buf, ftar_dtype dt, size_t i)
+{
+    if (dt == FTAR_FLOAT32) return ((const float *)buf)[i];
+    return dt == FTAR_BFLOAT16 ? from_bf16(((const uint16_t *)buf)[i]) : from_f16(((const uint16_t *)buf)[i]);
+}
+
+static int runmixed(int rd, size_t count, int calls, ftar_comm *comm, int wrank, int wsize, int dev, int multi)
+{
+    const char *pe = getenv("FTBENCH_PATTERN");
+    const int pattern = pe && atoi(pe) != 0;
+    float *h = malloc(count * sizeof(float)); /* the dense vector's values */
+    void *stage = malloc((count / (size_t)multi + 1) * sizeof(float));
+    if (!h || !stage) return 4;
+    for (size_t i = 0; i < count; i++) h[i] = pattern ? (float)((7 * i + 13 * (size_t)wrank) % 4) : (float)(wrank % 4);
+    static const void *ms_[FTAR_MULTI_MAX];
+    static void *mr_[FTAR_MULTI_MAX];
+    static size_t mc_[FTAR_MULTI_MAX];
+    static ftar_dtype mt_[FTAR_MULTI_MAX];
+    size_t off = 0;
+    for (int k = 0; k < multi; k++) {
+        mc_[k] = count / (size_t)multi + ((size_t)k < count % (size_t)multi);
+        mt_[k] = mixed_cycle[k % 3];
+        const size_t b = mc_[k] * (mt_[k] == FTAR_FLOAT32 ? 4 : 2);
+        for (size_t i = 0; i < mc_[k]; i++) mixed_put(stage, mt_[k], i, h[off + i]);
+        void *a = NULL;
+        CHECK_HIP(hipMalloc(&a, b));
+        CHECK_HIP(hipMalloc(&mr_[k], b));
+        CHECK_HIP(hipMemcpy(a, stage, b, hipMemcpyHostToDevice));
+        ms_[k] = a;
+        off += mc_[k];
+    }
+    CHECK_HIP(hipDeviceSynchronize());
+
+    double ms[MAX_CALLS], value[MAX_CALLS], hbm[MAX_CALLS];
+    int rc[MAX_CALLS], rec[MAX_CALLS], size_after[MAX_CALLS], uniform[MAX_CALLS], step0_copy = 0;
+    for (int c = 0; c < calls; c++) {
+        rc[c] = ftar_allreduce_multi_mixed(rd ? FTAR_ALGO_RD : FTAR_ALGO_RABENSEIFNER, ms_, mr_, mc_, mt_, multi, FTAR_SUM,
+                                           1.0f, comm);
+        ftar_stats st;
+        ftar_last_stats(comm, &st);
+        ms[c] = st.wall_s * 1e3;
+        hbm[c] = st.hbm_bytes;
+        rec[c] = st.recoveries;
+        size_after[c] = st.comm_size_after;
+        step0_copy |= st.step0_copy;
+        off = 0;
+        for (int k = 0; k < multi; off += mc_[k], k++) {
+            CHECK_HIP(hipMemcpy(stage, mr_[k], mc_[k] * (mt_[k] == FTAR_FLOAT32 ? 4 : 2), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < mc_[k]; i++) h[off + i] = mixed_get(stage, mt_[k], i);
+        }
+        value[c] = h[0];
+        uniform[c] = 1;
+        const int members = size_after[c];
+        for (size_t i = 0; i < count; i++) {
+            float want = h[0];
+            if (pattern) {
+                size_t sum = 0;
+                for (int q = 0; q < members; q++) sum += (7 * i + 13 * (size_t)q) % 4;
+                want = (float)sum;
+            }
+            if (h[i] != want) {
+                uniform[c] = 0;
+                break;
+            }
+        }
+    }
+    printf("{\"rank\": %d, \"size\": %d, \"device\": %d, \"step0_copy\": %d, \"calls\": [", wrank, wsize, dev,
+           step0_copy);
+    for (int c = 0; c < calls; c++)
+        printf("%s{\"rc\": %d, \"ms\": %.4f, \"recoveries\": %d, \"comm_size\": %d, \"value\": %.1f, \"uniform\": %s, "
+               "\"hbm_bytes\": %.0f}",
+               c ? ", " : "", rc[c], ms[c], rec[c], size_after[c], value[c], uniform[c] ? "true" : "false", hbm[c]);
+    printf("]}\n");
+    fflush(stdout);
+    ftar_finalize(comm);
+    for (int k = 0; k < multi; k++) {
+        (void)hipFree((void *)(uintptr_t)ms_[k]);
+        (void)hipFree(mr_[k]);
+    }
+    free(stage);
     free(h);
     return 0;
 }

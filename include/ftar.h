@@ -287,6 +287,43 @@ int ftar_allreduce_multi_acc32(ftar_algo algo, const void *const *sbufs, void *c
                                const size_t *counts, int nbufs,
                                ftar_dtype dtype, ftar_op op, float scale, ftar_comm *comm);
 
+/* The float32-accumulating list form for lists of MIXED float types: dtypes[i] is FTAR_FLOAT16,
+ * FTAR_BFLOAT16 or FTAR_FLOAT32, one per entry (a model's bf16 / fp16 gradients beside float32
+ * norms, biases and master copies, in one call); counts[i] is in elements of dtypes[i].  The
+ * result is exactly:
+ *   1. widen:  every element of sbufs[0] ++ sbufs[1] ++ ... becomes a float32 -- list order, in
+ *      elements, no padding; a float32 entry is copied, a 2-byte entry widened exactly as
+ *      ftar_allreduce_multi_acc32 widens it;
+ *   2. reduce: the plain FTAR_FLOAT32 Allreduce named by `algo` with `op` on that vector --
+ *      "exactly" as above: the bits, the recovery and abort outcomes, the comm re-targeting, the
+ *      FTAR_KILL call index (one call) and the return code;
+ *   3. scale and narrow: every element a becomes scale * a, one IEEE float32 multiplication
+ *      (round to nearest even, subnormals kept).  A float32 entry stores the product; a 2-byte
+ *      entry stores it after ONE conversion to its own type under ftar_allreduce_multi_acc32's
+ *      rules.  The scale is applied whatever the op;
+ *   4. scatter: the result is cut back into rbufs[i] at the same element offsets.
+ * The rules are ftar_allreduce_multi_acc32's, except:
+ *   - collective: every live rank passes the same counts AND dtypes;
+ *   - per-entry in place is allowed, outputs are pairwise disjoint -- checked on user bytes,
+ *     counts[i] x the entry's own element size; all inputs are read before any output is written;
+ *   - entries with counts[i] == 0 are skipped: neither their pointers nor dtypes[i] are looked at;
+ *   - there is never a straight-through case; a total of 0 elements returns what the plain
+ *     FTAR_FLOAT32 call with count == 0 returns;
+ *   - ftar_stats.coalesced is the number of non-empty entries; hbm_bytes counts, per launch and
+ *     element, 4 bytes plus the entry's own element size;
+ *   - entries need their own element's alignment: 2 or 4 bytes.
+ * Errors, in this order: comm NULL: FTAR_ERR_ARG.  Then the op check of FTAR_FLOAT32, whose op set
+ * all three types share (logical and bitwise ops, MAXLOC, MINLOC: FTAR_ERR_OP).  Then
+ * FTAR_ERR_ARG, before anything is launched or any barrier entered: a scale that is not finite,
+ * sbufs, rbufs, counts or dtypes NULL, nbufs < 1 or > FTAR_MULTI_MAX, an unknown algo, a
+ * non-empty entry whose dtype is not one of the three, a misaligned buffer, a buffer the device
+ * entry points would refuse, overlapping outputs, a build without the mover.  If the schedule
+ * returns an error no rbufs[i] is written.
+ * Costs what ftar_allreduce_multi_acc32 costs: 2 x 4 bytes x the largest total so far. */
+int ftar_allreduce_multi_mixed(ftar_algo algo, const void *const *sbufs, void *const *rbufs,
+                               const size_t *counts, const ftar_dtype *dtypes, int nbufs,
+                               ftar_op op, float scale, ftar_comm *comm);
+
 /* MPI_Reduce_local(in, inout, count, dtype, op) on the device:
  * inout[i] = in[i] (op) inout[i] with the reference's operand roles.
  * `stream` is a hipStream_t (NULL = null stream); the call is asynchronous.
