@@ -1,6 +1,6 @@
-// TEST-ONLY, host-only: the tables and inputs of gather_check (gather_kernel and gather_cvt_kernel,
-// the movers of ftar_allreduce_multi and ftar_allreduce_multi_acc32) and the cases of lds_check
-// (reduce_lds_kernel), shared with ref_check, whose selftest replays every table on the CPU and
+// TEST-ONLY, host-only: the tables and inputs of gather_check (gather_kernel, gather_cvt_kernel and
+// gather_mix_kernel, the movers of ftar_allreduce_multi, ftar_allreduce_multi_acc32 and
+// ftar_allreduce_multi_mixed) and the cases of lds_check (reduce_lds_kernel), shared with ref_check, whose selftest replays every table on the CPU and
 // asserts that the matrices reach what they are meant to reach and that the scatter inputs can
 // tell a wrong narrowing from the right one (tests/test_kernel_ref.py).
 //
@@ -11,7 +11,8 @@
 // A table lives in one arena (256-byte aligned): a guard, the packed vector `pbase` bytes past a
 // 256-byte boundary, a guard, then one 256-byte aligned slot per entry whose user buffer starts
 // kGuard + uoff bytes into it.  A `pinned` table keeps its slots in a second arena of pinned host
-// memory, laid out the same way from offset 0.
+// memory, laid out the same way from offset 0.  A mixed table (mix_tables()) gives every entry a
+// type of its own: its packed side counts 4 bytes per element, its user side the type's own size.
 #pragma once
 
 #include <cmath>
@@ -47,7 +48,10 @@ struct Table {
     size_t nlead = 0;   // ... and how many of them (the rest is the mixed fill)
     std::vector<size_t> cnt; // elements per entry
     std::vector<int> uoff;   // user buffer's byte offset past a 16-byte boundary
-    size_t ues() const { return cvt ? 2 : es; }
+    std::vector<int> ty;     // a mixed table: kFloat16, kBFloat16 or kFloat32 per entry; empty: uniform
+    bool mixed() const { return !ty.empty(); }
+    bool two_byte(size_t e) const { return ty.empty() ? cvt : ty[e] != kFloat32; }
+    size_t ues(size_t e) const { return ty.empty() ? (cvt ? 2 : es) : (ty[e] == kFloat32 ? 4 : 2); } // user bytes per element
     size_t elems() const
     {
         size_t n = 0;
@@ -60,6 +64,8 @@ struct Table {
 struct Layout {
     size_t packed_at = 0, total = 0;
     std::vector<size_t> off, first; // packed byte offset and first element of every entry
+    std::vector<size_t> sub;        // first element counted among those of the entry's kind (2-byte, or not)
+    size_t n16 = 0, n32 = 0;        // elements of 2-byte entries / of the others
     std::vector<size_t> user_at;    // in the device arena, or in the pinned one
     size_t dev_bytes = 0, host_bytes = 0;
 };
@@ -72,6 +78,9 @@ inline Layout layout(const Table &T)
     for (size_t c : T.cnt) {
         L.off.push_back(o);
         L.first.push_back(e0);
+        size_t &kind = T.two_byte(L.sub.size()) ? L.n16 : L.n32;
+        L.sub.push_back(kind);
+        kind += c;
         o += c * T.es;
         e0 += c;
     }
@@ -80,7 +89,7 @@ inline Layout layout(const Table &T)
     size_t &next = T.pinned ? host : dev;
     for (size_t i = 0; i < T.cnt.size(); i++) {
         L.user_at.push_back(next + kGuard + (size_t)T.uoff[i]);
-        next += round256(T.cnt[i] * T.ues() + 16 + 2 * kGuard);
+        next += round256(T.cnt[i] * T.ues(i) + 16 + 2 * kGuard);
     }
     L.dev_bytes = dev;
     L.host_bytes = host;
@@ -121,7 +130,7 @@ inline std::vector<size_t> main_counts(unsigned es, bool cvt)
 
 inline unsigned align_of(unsigned es) { return es < 8 ? es : (es == 8 ? 4 : 8); } // 8-byte pairs: 4; the 16-byte pair: 8
 
-enum Mode { kSame, kCo, kOwn, kOddMix, kClass };
+enum Mode { kSame, kCo, kOwn, kOddMix, kClass, kMixCo, kMixOff };
 
 // user offsets of a table whose counts and pbase are set.  kSame: every entry at `arg`; kCo: every
 // entry congruent to its packed address mod 16 (the vector path everywhere); kOwn: entry i at its
@@ -143,6 +152,7 @@ inline void set_offsets(Table &T, Mode mode, int arg)
         case kOwn: u = (int)((i * 7 % 16) / a * a); break;
         case kOddMix: u = i % 3 == 0 ? (int)(pa & 15) : (int)((i * 6) & 14); break;
         case kClass: u = (int)(2 * ((pa / 4 + 8 - (size_t)arg) & 7)); break;
+        default: break; // (the mixed tables' modes: set_mix_offsets)
         }
         T.uoff.push_back(u);
         o += T.cnt[i] * T.es;
@@ -181,7 +191,7 @@ inline Table make(const std::string &name, unsigned es, bool cvt, const std::vec
 inline std::vector<Table> plain_tables()
 {
     std::vector<Table> out;
-    for (unsigned es : {2u, 4u, 8u, 16u}) {
+    for (unsigned es : {2u, 4u, 8u, 16u, 1u}) { // (1: the 8-bit integers, appended behind the older tables)
         const unsigned a = align_of(es);
         const std::string s = "es" + std::to_string(es);
         const std::vector<size_t> main = main_counts(es, false), ones = ones_counts(es), many = max_counts();
@@ -242,6 +252,148 @@ inline std::vector<Table> cvt_tables()
         T.block = kNonFinite;
         T.nlead = T.elems();
         out.push_back(T);
+    }
+    return out;
+}
+
+// ---- mixed tables (gather_mix_kernel) ---------------------------------------------------------
+// Packed offsets and sizes count 4 bytes per element for every entry (es = 4), the user side 2 or
+// 4.  kSame: every entry at `arg`, a float32 entry at `arg` rounded down to a multiple of 4; kOwn as
+// above with the entry's own alignment; kMixCo: every float32 entry congruent to its packed address
+// mod 16 (the vector path) and every 2-byte entry of class 8; kMixOff: no float32 entry congruent
+// (words throughout), the 2-byte ones of class 4, 2 and 1 in turn.
+inline const char *type_name(int dt) { return dt == kFloat16 ? "float16" : dt == kBFloat16 ? "bfloat16" : "float32"; }
+inline int type_index(int dt) { return dt == kFloat16 ? 0 : dt == kBFloat16 ? 1 : 2; }
+static const int kMixTypes[3] = {kFloat16, kBFloat16, kFloat32};
+
+inline void set_mix_offsets(Table &T, Mode mode, int arg)
+{
+    static const size_t diff[5] = {4, 2, 1, 6, 3}; // element-index differences: class 4, 2, 1, 2, 1
+    size_t o = 0;
+    T.uoff.clear();
+    for (size_t i = 0; i < T.cnt.size(); i++) {
+        const size_t pa = T.pbase + o, turn = i + i / 3;
+        const bool f32 = T.ty[i] == kFloat32;
+        const int a = f32 ? 4 : 2;
+        int u = 0;
+        switch (mode) {
+        case kSame: u = arg / a * a; break;
+        case kOwn: u = (int)(i * 7 % 16) / a * a; break;
+        case kMixCo: u = f32 ? (int)(pa & 15) : (int)(2 * ((pa / 4) & 7)); break;
+        default: u = f32 ? (int)((pa + 4 + 4 * (turn % 3)) & 15) : (int)(2 * ((pa / 4 + 8 - diff[turn % 5]) & 7)); break;
+        }
+        T.uoff.push_back(u);
+        o += T.cnt[i] * 4;
+    }
+}
+
+inline std::vector<int> type_cycle(size_t n, const std::vector<int> &period, size_t start = 0)
+{
+    std::vector<int> ty(n);
+    for (size_t i = 0; i < n; i++) ty[i] = period[(i + start) % period.size()];
+    return ty;
+}
+
+inline Table make_mix(const std::string &name, const std::vector<size_t> &cnt, const std::vector<int> &ty, size_t pbase, Mode mode,
+                      int arg, bool pinned = false)
+{
+    Table T;
+    T.name = name;
+    T.es = 4;
+    T.cnt = cnt;
+    T.ty = ty;
+    T.pbase = pbase;
+    T.pinned = pinned;
+    uint64_t h = 0x3a1d7ull;
+    for (char c : name) h = mix(h ^ (unsigned char)c);
+    T.seed = h;
+    set_mix_offsets(T, mode, arg);
+    return T;
+}
+
+// the 2-byte entries of a value table with float32 entries of 1, 5 and 4099 elements between them
+inline void interleave_f32(const std::vector<size_t> &c16, int dt16, std::vector<size_t> *cnt, std::vector<int> *ty)
+{
+    static const size_t between[3] = {1, 5, 4099};
+    for (size_t i = 0; i < c16.size(); i++) {
+        if (i) {
+            cnt->push_back(between[(i - 1) % 3]);
+            ty->push_back(kFloat32);
+        }
+        cnt->push_back(c16[i]);
+        ty->push_back(dt16);
+    }
+}
+
+inline std::vector<Table> mix_tables()
+{
+    std::vector<Table> out;
+    const std::vector<int> three(kMixTypes, kMixTypes + 3);
+    const std::vector<size_t> main = main_counts(4, true), ones = ones_counts(4), many = max_counts();
+    const size_t starts[5] = {0, 4, 8, 12, 20}, T = kTile / 4;
+    // main: every size with every type (the cycle started at each), every user offset, the packed
+    // starts that give a congruent float32 entry heads of 0, 3, 2 and 1 words.  Entry 17 (one tile)
+    // is float32 in cycle 0, entry 21 (five tiles + 3, starting 12 bytes behind a tile edge) in
+    // cycle 2: whole tiles of 1024 vectors at packed start 0, of 1023 with head and tail at 4.
+    for (size_t s = 0; s < 3; s++) {
+        const std::string c = "mix main cycle " + std::to_string(s);
+        const std::vector<int> ty = type_cycle(main.size(), three, s);
+        for (int m = 0; m < 16; m += 2) out.push_back(make_mix(c + " same " + std::to_string(m), main, ty, starts[(m / 2 + s) % 5], kSame, m));
+        out.push_back(make_mix(c + " own", main, ty, starts[(s + 3) % 5], kOwn, 0, s == 1)); // (cycle 1: pinned)
+        for (size_t pb : starts) out.push_back(make_mix(c + " co " + std::to_string(pb), main, ty, pb, kMixCo, 0));
+        out.push_back(make_mix(c + " off", main, ty, starts[s + 1], kMixOff, 0));
+    }
+    // ones: with a period of 3 every (wave, type) pair occurs; with {f16, f32, bf16, f32} every wave
+    // sees one type only -- an index by wave where the entry's is meant shows in one of the two
+    out.push_back(make_mix("mix ones period 3 co", ones, type_cycle(ones.size(), three), 12, kMixCo, 0));
+    out.push_back(make_mix("mix ones period 3 own pinned", ones, type_cycle(ones.size(), three, 1), 0, kOwn, 0, true));
+    out.push_back(make_mix("mix ones period 4 own", ones, type_cycle(ones.size(), {kFloat16, kFloat32, kBFloat16, kFloat32}), 4, kOwn, 0));
+    out.push_back(make_mix("mix ones period 4 co", ones, type_cycle(ones.size(), {kFloat16, kFloat32, kBFloat16, kFloat32}), 8, kMixCo, 0));
+    // the type array begins 24 n bytes behind the table: n = 1024, 1023 and 7
+    out.push_back(make_mix("mix max own", many, type_cycle(many.size(), three), 8, kOwn, 0));
+    out.push_back(make_mix("mix max co", many, type_cycle(many.size(), three, 2), 20, kMixCo, 0));
+    out.push_back(make_mix("mix 1023 entries", std::vector<size_t>(many.begin(), many.begin() + 1023), type_cycle(1023, three, 1), 4, kOwn, 0));
+    out.push_back(make_mix("mix 7 entries", std::vector<size_t>(many.begin(), many.begin() + 7), type_cycle(7, three, 2), 12, kMixCo, 0));
+    // a tile edge exactly between two types, and one 3 elements before the first type's end; two
+    // neighbours of one type behind them
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) {
+            if (a == b) continue;
+            const int A = kMixTypes[a], B = kMixTypes[b];
+            const std::string ab = std::string(type_name(A)) + " | " + type_name(B);
+            out.push_back(make_mix("mix edge between " + ab, {7, T - 7, 600, 9, 5}, {B, A, B, A, A}, starts[(size_t)(a + b) % 5], a < b ? kMixCo : kOwn, 0));
+            out.push_back(make_mix("mix edge inside " + ab, {7, T - 4, 600, 9, 5}, {B, A, B, A, A}, starts[(size_t)(a + 2 * b) % 5], a < b ? kOwn : kMixCo, 0));
+        }
+    // the kWavePiece threshold in packed bytes: 1020, 1024, 1028 for every type, next to each other
+    // in one tile; the three one-wave pieces (entries 0, 3, 6) on waves 0, 3 and 2
+    {
+        std::vector<size_t> c;
+        std::vector<int> ty;
+        for (int t : kMixTypes)
+            for (size_t n : {(size_t)255, (size_t)256, (size_t)257}) {
+                c.push_back(n);
+                ty.push_back(t);
+            }
+        out.push_back(make_mix("mix thresholds co", c, ty, 0, kMixCo, 0));
+        out.push_back(make_mix("mix thresholds off", c, ty, 8, kMixOff, 0));
+    }
+    // the converting tables' value blocks in the 2-byte entries (every pattern; every tie; infinities
+    // and NaNs), once per 2-byte type, with float32 entries between them
+    for (int dt : {(int)kFloat16, (int)kBFloat16}) {
+        const std::string t = type_name(dt);
+        struct { const char *name; std::vector<size_t> c16; size_t pbase; int block; size_t nlead; } v[3] = {
+            {"mix patterns ", {1, 4095, 4099, 8189, 16384, 32768 - 13, 13, 5000}, 4, kPatterns, 65536},
+            {"mix ties ", {3 * 4096 + 1, 3 * 20000, 3 * 41436 - 1, 7000}, 16, kTies, 3 * 65536},
+            {"mix nonfinite ", {61, 70, 1, 69}, 8, kNonFinite, 201}};
+        for (const auto &b : v) {
+            std::vector<size_t> c;
+            std::vector<int> ty;
+            interleave_f32(b.c16, dt, &c, &ty);
+            Table V = make_mix(b.name + t, c, ty, b.pbase, kOwn, 0);
+            V.block = b.block;
+            V.nlead = b.nlead;
+            out.push_back(V);
+        }
     }
     return out;
 }
@@ -396,6 +548,58 @@ inline uint16_t narrow_ref(float a, float scale, int dt, int how = kContract)
     if (how == kUpperHalf && scale != 0.0f && (bits_of(a) & 0x7fff0000u) == 0x7f800000u)
         return (uint16_t)(((bits_of(a) ^ bits_of(scale)) >> 31 << 15) | inf16(dt));
     return encode16((double)prod, dt, how >= 1 && how <= 3 ? (Round)how : kNearestEven);
+}
+
+// ---- mixed mover: the float32 entries ----------------------------------------------------------
+// gather: word i of entry e's user buffer -- arbitrary bits, one in eight a signalling NaN and one
+// in eight a quiet NaN with a payload.  A gather is a copy: the expectation is the same bits.
+inline uint32_t f32_user(const Table &T, size_t e, size_t i)
+{
+    uint32_t w = 0;
+    for (size_t b = 0; b < 4; b++) w |= (uint32_t)plain_byte(T.seed, e, 4 * i + b) << (8 * b);
+    const uint64_t h = mix(T.seed ^ mix(0xf32ull + e * 0x9e3779b97f4a7c15ull + i));
+    if (h % 8 == 0) return (w & 0x803fffffu) | 0x7f800000u | 1u; // signalling: the quiet bit clear
+    if (h % 8 == 1) return w | 0x7fc00000u;
+    return w;
+}
+inline bool signalling(uint32_t w) { return (w & 0x7fc00000u) == 0x7f800000u && (w & 0x003fffffu); }
+
+// scatter: packed float32 element g (counted among the float32 elements) at this scale
+inline float f32_packed(const Table &T, float scale, size_t g)
+{
+    const uint64_t h = mix(T.seed ^ mix(((uint64_t)kFloat32 << 56) ^ g)), h2 = mix(h);
+    const unsigned c = (unsigned)(h % 64), sgn = (unsigned)(h >> 8) & 1;
+    const bool neg_scale = std::signbit(scale);
+    auto sign = [&](float v) { return sgn ? -v : v; };
+    if (c < 2) return sign(0.0f);
+    if (c < 6) { // a product in float32's subnormal range
+        const float t = f32_of((uint32_t)(0x00010000u + (h2 % 0x007f0000u)));
+        return scale == 0x1p-12f ? sign(t * 0x1p12f) : toward(sign(t), scale);
+    }
+    if (c < 9) // -0, and values whose product is negative and underflows to -0 at the small scales
+        switch ((h >> 16) % 3) {
+        case 0: return neg_scale ? 0.0f : -0.0f;
+        case 1: return neg_scale ? f32_of(1) : f32_of(0x80000001u);
+        default: return f32_of((neg_scale ? 0u : 0x80000000u) | (1u + (uint32_t)(h2 % 0x3f)));
+        }
+    if (c < 11) return sign(f32_of(0x7eaaaaaau + 256u + (uint32_t)(h2 % 1000))); // a third of the largest value and a bit: overflows at 3.0000002
+    if (c == 11) return sign(INFINITY);                                             // a NaN at scale 0
+    if (c == 12) return f32_of(0x7fc00000u | (uint32_t)(h2 & 0x803fffffu));
+    if (c == 13) return f32_of(0x7f800000u | (uint32_t)(h2 & 0x803fffffu) | 1u);  // signalling
+    if (c == 14) return sign(3.4028234663852886e38f);
+    return sign(f32_of((uint32_t)((127 - 16 + (h2 >> 32) % 31) << 23) | (uint32_t)(h2 & 0x7fffff))); // 2^-16 .. 2^15, a full mantissa
+}
+
+// The contract of a float32 entry (include/ftar.h): ONE float32 multiplication.  Mutants: the
+// Narrow ones that apply (kPlusZero) and two of its own.
+enum ScaleMutant { kFlushProduct = 7, kNotScaled = 8 };
+inline uint32_t scale_ref(float a, float scale, int how = kContract)
+{
+    if (how == kNotScaled) return bits_of(a);
+    const float prod = (float)((double)scale * (double)a);
+    if (how == kPlusZero && prod == 0.0f) return 0;
+    if (how == kFlushProduct && prod != 0.0f && std::fabs(prod) < 0x1p-126f) return bits_of(prod) & 0x80000000u;
+    return bits_of(prod);
 }
 
 // ---- reduce_lds_kernel cases -----------------------------------------------------------------

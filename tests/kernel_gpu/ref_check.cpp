@@ -35,7 +35,24 @@
 //       * in no such case (the block of infinities and NaNs apart) more than 1/8 of the expected
 //         elements are NaN, and at least half are finite and non-zero except at scale 0;
 //       * every order-sensitive lds_check case expects, in its full tiles and in its ragged rest
-//         alike (where they hold 257 elements or more), a byte that swapped operands would change.
+//         alike (where they hold 257 elements or more), a byte that swapped operands would change;
+//       * the mixed tables (gather_check mix) are replayed the same way with every entry going by
+//         its own type, as in gather_mix_kernel, and must reach, for each of the three types, a
+//         workgroup's piece, a small piece on each wave, a tile ending inside an entry and at its
+//         end with each other type behind it, a piece in a workgroup's second tile or later and
+//         pieces of exactly 1020 / 1024 / 1028 packed bytes; every ordered pair of neighbouring
+//         types inside one tile; every converting class for both 2-byte types; for float32 a
+//         vector piece with body, tail and a head of 1, 2 and 3 words, a piece that is not a vector
+//         piece, the unrolled loop at 256 threads and its remainder, nvec = 1023 and 1024, a word
+//         loop at 64 and at 256 threads; a pinned table and one of 1024 entries;
+//       * every mixed scatter case (table x scale, scale not 0) meets the converting conditions on
+//         its 2-byte elements where it has 257 of them, and where it has 257 float32 elements
+//         expects one that a subnormal product flushed to zero would change and, unless the scale
+//         is 1, one that a missing multiplication would; over the matrix both of these and a -0
+//         product that a +0 would miss occur in an element that moves as a word and in one that
+//         moves in a 16-byte vector, -0 alone and in a group for both 2-byte types, a NaN whose
+//         upper half reads as an infinity, and among the float32 words to gather a signalling NaN
+//         in a word and in a vector; the NaN and finite shares hold as above.
 //   ref_check narrow DTYPE IN OUT   OUT = the float32 file IN narrowed once (the reference of the
 //       converting scatter at scale 1), 2 bytes per element
 #include <cmath>
@@ -182,6 +199,15 @@ struct Cover {
     Loops loops;
 };
 
+// what only a mixed table can reach; a type is indexed 0: float16, 1: bfloat16, 2: float32
+struct MixCover {
+    size_t big[3] = {}, small_wave[3][4] = {}, inside[3] = {}, at_end[3][3] = {}, later_tile[3] = {}, next_to[3][3] = {};
+    size_t cls_ht[2][4] = {};                                  // per 2-byte type, as Cover's
+    size_t f_hbt[4] = {}, f_nonvec = 0, f_words[2] = {0, 0};   // float32: head of 1, 2, 3 words with body and tail; word loops at 64 / 256 threads
+    Loops f_loops;                                             // float32: the loops over 16-byte vectors
+    size_t threshold[3][3] = {};                               // pieces of exactly 1020, 1024, 1028 packed bytes
+};
+
 std::vector<ftar::GEntry> entries(const Table &T, const Layout &L)
 {
     std::vector<ftar::GEntry> tab(T.cnt.size());
@@ -190,8 +216,12 @@ std::vector<ftar::GEntry> entries(const Table &T, const Layout &L)
     return tab;
 }
 
-// the kernels' walk; `path` (converting tables): 1 where an element moves alone, 2 in a group
-int replay(const Table &T, unsigned grid, Cover &C, std::vector<unsigned char> *path)
+// the kernels' walk; `path` (converting and mixed tables): 1 where an element moves alone (a 2-byte
+// element outside a group, a float32 word of a head, a tail or a piece that is not a vector piece),
+// 2 in a group or a 16-byte vector.  A mixed table's entry goes by its own type, as in
+// gather_mix_kernel: float32 through gather_piece with es = 4, a 2-byte one through cvt_piece, the
+// workgroup's piece or a wave's decided from pe - pb.
+int replay(const Table &T, unsigned grid, Cover &C, std::vector<unsigned char> *path, MixCover *M = nullptr)
 {
     const Layout L = layout(T);
     const std::vector<ftar::GEntry> tab = entries(T, L);
@@ -203,9 +233,24 @@ int replay(const Table &T, unsigned grid, Cover &C, std::vector<unsigned char> *
         unsigned mine = 0;
         for (unsigned t = b; t < ntiles; t += grid, mine++) {
             const size_t lo = (size_t)t * ftar::kTileBytes, hi = lo + ftar::kTileBytes < L.total ? lo + ftar::kTileBytes : L.total;
+            int prev = -1; // the entry in front, where it had a piece in this tile
             for (int e = ftar::gather_first(tab.data(), n, lo); e < n; e++) {
                 size_t poff, bytes;
-                if (T.cvt) {
+                const int ti = M ? type_index(T.ty[(size_t)e]) : 0;
+                if (M) {
+                    const size_t pb = tab[e].off > lo ? tab[e].off : lo, pe = tab[e].off + tab[e].bytes < hi ? tab[e].off + tab[e].bytes : hi;
+                    if (pb >= pe) break;
+                    const bool big = pe - pb >= kWave;
+                    if (big) M->big[ti]++;
+                    else M->small_wave[ti][e & 3]++;
+                    for (int k = 0; k < 3; k++) M->threshold[ti][k] += pe - pb == 1020 + 4 * (size_t)k;
+                    M->later_tile[ti] += mine >= 1;
+                    if (prev >= 0) M->next_to[type_index(T.ty[(size_t)prev])][ti]++;
+                    if (tab[e].off + tab[e].bytes > hi) M->inside[ti]++;
+                    else if (tab[e].off + tab[e].bytes == hi && e + 1 < n) M->at_end[ti][type_index(T.ty[(size_t)e + 1])]++;
+                }
+                prev = e;
+                if (T.two_byte((size_t)e)) {
                     ftar::CPiece P;
                     if (!ftar::cvt_piece(tab[e], lo, hi, packed, &P)) break;
                     poff = P.poff;
@@ -213,6 +258,7 @@ int replay(const Table &T, unsigned grid, Cover &C, std::vector<unsigned char> *
                     const unsigned nth = bytes >= kWave ? 256 : 64;
                     const size_t tail = P.k == 1 ? 0 : P.n - P.head - P.nvec * P.k;
                     C.cls_ht[P.k == 8 ? 0 : P.k == 4 ? 1 : P.k == 2 ? 2 : 3] += P.k == 1 || (P.head && P.nvec && tail);
+                    if (M) M->cls_ht[ti][P.k == 8 ? 0 : P.k == 4 ? 1 : P.k == 2 ? 2 : 3] += P.k == 1 || (P.head && P.nvec && tail);
                     C.loops.add(P.head, nth);
                     if (P.k > 1) {
                         C.loops.add(P.nvec, nth);
@@ -229,7 +275,19 @@ int replay(const Table &T, unsigned grid, Cover &C, std::vector<unsigned char> *
                     C.unit[P.unit == 1 ? 0 : P.unit == 2 ? 1 : P.unit == 4 ? 2 : 3]++;
                     C.vec_hbt += P.vec && P.head && P.nvec && P.bytes - P.head - 16 * P.nvec;
                     C.nonvec += !P.vec;
-                    if (P.vec) C.loops.add(P.nvec, bytes >= kWave ? 256 : 64);
+                    const unsigned nth = bytes >= kWave ? 256 : 64;
+                    if (M) { // scale_piece / move_piece<false> on words and 16-byte vectors
+                        const size_t tail = P.vec ? P.bytes - P.head - 16 * P.nvec : 0;
+                        if (P.vec && P.nvec && tail) M->f_hbt[P.head / 4]++;
+                        M->f_nonvec += !P.vec;
+                        M->f_words[nth == 256] += (P.head != 0) + (tail != 0);
+                        if (P.vec) M->f_loops.add(P.nvec, nth);
+                        if (path)
+                            for (size_t i = 0; i < P.bytes / 4; i++)
+                                (*path)[poff / 4 + i] = (!P.vec || 4 * i < P.head || 4 * i >= P.head + 16 * P.nvec) ? 1 : 2;
+                    } else if (P.vec) {
+                        C.loops.add(P.nvec, nth);
+                    }
                 }
                 C.pieces++;
                 if (bytes >= kWave) C.big++;
@@ -411,6 +469,187 @@ int movers_selftest()
     return failed;
 }
 
+// the tables of gather_check mix: what they reach, and what their scatter inputs can tell
+int mixed_selftest()
+{
+    int failed = 0;
+    static const char *tn[3] = {"float16", "bfloat16", "float32"};
+    auto need_t = [&](const char *what, int a, int b, size_t v) {
+        if (v) return;
+        failed++;
+        if (b < 0) printf("FAIL the mixed tables never reach: %s (%s)\n", what, tn[a]);
+        else printf("FAIL the mixed tables never reach: %s (%s, then %s)\n", what, tn[a], tn[b]);
+    };
+    // ---- coverage ----
+    Cover X;
+    MixCover M;
+    const std::vector<Table> tabs = mix_tables();
+    std::vector<std::vector<unsigned char>> paths;
+    size_t pinned = 0, full = 0;
+    for (const Table &T : tabs) {
+        pinned += T.pinned;
+        full += T.cnt.size() == (size_t)ftar::kMaxGather;
+        const Layout L = layout(T);
+        paths.emplace_back(T.elems(), 0);
+        bool first = true;
+        for (unsigned g : grids((unsigned)((L.total + kTile - 1) / kTile))) {
+            failed += replay(T, g, X, first ? &paths.back() : nullptr, &M);
+            first = false;
+        }
+    }
+    printf("selftest: %zu mixed tables (%zu pinned, %zu of %d entries); each runs in both directions\n", tabs.size(), pinned, full,
+           ftar::kMaxGather);
+    printf("selftest: mixed: %zu pieces; workgroups with >= 2 tiles %zu; 2-byte groups: unrolled loop at 64 / 256 threads %zu / %zu, "
+           "remainder %zu / %zu\n", X.pieces, X.wg_two_tiles, X.loops.unrolled[0], X.loops.unrolled[1], X.loops.rest[0], X.loops.rest[1]);
+    for (int t = 0; t < 3; t++) {
+        printf("selftest: mixed %s: the workgroup's pieces %zu, small on wave 0 / 1 / 2 / 3: %zu / %zu / %zu / %zu; tiles ending inside an "
+               "entry %zu, at its end with %s / %s behind %zu / %zu; pieces in a workgroup's later tiles %zu; pieces of 1020 / 1024 / "
+               "1028 bytes %zu / %zu / %zu\n", tn[t], M.big[t], M.small_wave[t][0], M.small_wave[t][1], M.small_wave[t][2],
+               M.small_wave[t][3], M.inside[t], tn[(t + 1) % 3], tn[(t + 2) % 3], M.at_end[t][(t + 1) % 3], M.at_end[t][(t + 2) % 3],
+               M.later_tile[t], M.threshold[t][0], M.threshold[t][1], M.threshold[t][2]);
+        printf("selftest: mixed %s: in one tile behind float16 / bfloat16 / float32: %zu / %zu / %zu\n", tn[t], M.next_to[0][t],
+               M.next_to[1][t], M.next_to[2][t]);
+    }
+    for (int t = 0; t < 2; t++)
+        printf("selftest: mixed %s: class 8 / 4 / 2 with head, groups and tail: %zu / %zu / %zu, class 1: %zu\n", tn[t], M.cls_ht[t][0],
+               M.cls_ht[t][1], M.cls_ht[t][2], M.cls_ht[t][3]);
+    printf("selftest: mixed float32: vector pieces with body, tail and a head of 1 / 2 / 3 words: %zu / %zu / %zu, not vector %zu; "
+           "unrolled loop at 256 threads %zu, remainder %zu; nvec = 1023 / 1024: %zu / %zu; word loops at 64 / 256 threads %zu / %zu\n",
+           M.f_hbt[1], M.f_hbt[2], M.f_hbt[3], M.f_nonvec, M.f_loops.unrolled[1], M.f_loops.rest[1], M.f_loops.end_m1[1],
+           M.f_loops.end_0[1], M.f_words[0], M.f_words[1]);
+    failed += need("a pinned mixed table", pinned) + need("a mixed table of 1024 entries", full);
+    for (int t = 0; t < 3; t++) {
+        need_t("a piece of the workgroup", t, -1, M.big[t]);
+        for (int w = 0; w < 4; w++) need_t("a small piece on each wave", t, -1, M.small_wave[t][w]);
+        need_t("a tile ending inside an entry", t, -1, M.inside[t]);
+        need_t("a piece in a workgroup's second tile or later", t, -1, M.later_tile[t]);
+        static const char *thr[3] = {"a piece of 1020 packed bytes", "a piece of 1024 packed bytes", "a piece of 1028 packed bytes"};
+        for (int k = 0; k < 3; k++) need_t(thr[k], t, -1, M.threshold[t][k]);
+        for (int u = 0; u < 3; u++) {
+            if (u != t) need_t("a tile ending at an entry's end with another type behind it", t, u, M.at_end[t][u]);
+            need_t("two neighbours inside one tile", t, u, M.next_to[t][u]);
+        }
+    }
+    for (int t = 0; t < 2; t++)
+        for (int k = 0; k < 4; k++) need_t("every converting class with head and tail", t, -1, M.cls_ht[t][k]);
+    for (int h = 1; h < 4; h++) failed += need("a float32 vector piece with body, tail and every head of 1, 2, 3 words", M.f_hbt[h]);
+    failed += need("a float32 piece that is not a vector piece", M.f_nonvec) +
+              need("float32: the unrolled loop at 256 threads", M.f_loops.unrolled[1]) + need("float32: its remainder", M.f_loops.rest[1]) +
+              need("float32: nvec = 1023", M.f_loops.end_m1[1]) + need("float32: nvec = 1024", M.f_loops.end_0[1]) +
+              need("float32: a word loop at 64 threads", M.f_words[0]) + need("float32: a word loop at 256 threads", M.f_words[1]);
+
+    // ---- the gather inputs of the float32 entries: a signalling NaN as a word and inside a vector ----
+    size_t snan[2] = {0, 0};
+    for (size_t ti = 0; ti < tabs.size(); ti++) {
+        const Table &T = tabs[ti];
+        const Layout L = layout(T);
+        for (size_t e = 0; e < T.cnt.size(); e++)
+            if (!T.two_byte(e))
+                for (size_t i = 0; i < T.cnt[e]; i++)
+                    if (signalling(f32_user(T, e, i))) snan[paths[ti][L.first[e] + i] == 2]++;
+    }
+    failed += need("a signalling NaN gathered as a word", snan[0]) + need("a signalling NaN gathered in a 16-byte vector", snan[1]);
+
+    // ---- the scatter inputs against the mutants, per case (table x scale) ----
+    static const char *names[4] = {"rounding toward zero goes unseen", "ties away from zero go unseen",
+                                   "flushed subnormal results go unseen", "a fused multiply-convert goes unseen"};
+    size_t cases = 0, judged16 = 0, judged32 = 0, min_mut[4] = {SIZE_MAX, SIZE_MAX, SIZE_MAX, SIZE_MAX}, upper_half = 0;
+    size_t neg_zero[2][2] = {{0, 0}, {0, 0}};                                 // 2-byte: [type][alone, in a group]
+    size_t min_flush = SIZE_MAX, min_unscaled = SIZE_MAX;                     // float32, per case
+    size_t flush_at[2] = {0, 0}, unscaled_at[2] = {0, 0}, zero_at[2] = {0, 0}; // float32, over the matrix: [word, vector]
+    double max_nan = 0, min_finite = 1;
+    for (size_t ti = 0; ti < tabs.size(); ti++) {
+        const Table &T = tabs[ti];
+        const Layout L = layout(T);
+        const size_t n = T.elems();
+        for (float scale : kScales) {
+            cases++;
+            size_t nan = 0, fin = 0, mut[4] = {0, 0, 0, 0}, flush = 0, unscaled = 0;
+            for (size_t e = 0; e < T.cnt.size(); e++)
+                for (size_t i = 0; i < T.cnt[e]; i++) {
+                    const size_t g = L.sub[e] + i;
+                    const int way = paths[ti][L.first[e] + i] == 2;
+                    if (T.two_byte(e)) {
+                        const int dt = T.ty[e];
+                        const float a = cvt_packed(T, dt, scale, g);
+                        const uint16_t w = narrow_ref(a, scale, dt);
+                        const double v = decode16(w, dt);
+                        nan += std::isnan(v);
+                        fin += std::isfinite(v) && v != 0.0;
+                        if (std::isnan(v)) {
+                            upper_half += !is_nan16(narrow_ref(a, scale, dt, kUpperHalf), dt);
+                            continue;
+                        }
+                        for (int m = 0; m < 4; m++) mut[m] += narrow_ref(a, scale, dt, m + 1) != w;
+                        if (scale != 0.0f && w == 0x8000) neg_zero[dt == kBFloat16][way]++;
+                    } else {
+                        const float a = f32_packed(T, scale, g);
+                        const uint32_t w = scale_ref(a, scale);
+                        const float v = f32_of(w);
+                        nan += std::isnan(v);
+                        fin += std::isfinite(v) && v != 0.0f;
+                        if (std::isnan(v) || scale == 0.0f) continue; // NaN: compared by NaN-ness, every mutant gives one as well
+                        const bool f = scale_ref(a, scale, kFlushProduct) != w, u = scale_ref(a, scale, kNotScaled) != w;
+                        flush += f;
+                        unscaled += u;
+                        flush_at[way] += f;
+                        unscaled_at[way] += u;
+                        zero_at[way] += scale_ref(a, scale, kPlusZero) != w;
+                    }
+                }
+            const double sn = (double)nan / (double)n, sf = (double)fin / (double)n;
+            auto bad = [&](const char *why) {
+                failed++;
+                printf("FAIL %s scale %.9g: %s\n", T.name.c_str(), scale, why);
+            };
+            if (T.block != kNonFinite) {
+                if (sn > max_nan) max_nan = sn;
+                if (nan * 8 > n) bad("more than 1/8 of the expected elements are NaN");
+            }
+            if (scale == 0.0f) continue;
+            if (n >= 257) {
+                if (sf < min_finite) min_finite = sf;
+                if (fin * 2 < n) bad("fewer than half of the expected elements are finite and non-zero");
+            }
+            if (L.n16 >= 257) {
+                judged16++;
+                for (int m = 0; m < 4; m++) {
+                    if (m == 3 && exact_scale(scale)) continue;
+                    if (mut[m] < min_mut[m]) min_mut[m] = mut[m];
+                    if (!mut[m]) bad(names[m]);
+                }
+            }
+            if (L.n32 >= 257) {
+                judged32++;
+                if (flush < min_flush) min_flush = flush;
+                if (!flush) bad("a float32 subnormal product flushed to zero goes unseen");
+                if (scale != 1.0f) {
+                    if (unscaled < min_unscaled) min_unscaled = unscaled;
+                    if (!unscaled) bad("a float32 entry that is not scaled goes unseen");
+                }
+            }
+        }
+    }
+    printf("selftest: %zu mixed scatter cases at a scale other than 0: %zu with >= 257 2-byte elements, %zu with >= 257 float32 elements\n",
+           cases - tabs.size(), judged16, judged32);
+    printf("selftest: mixed: largest NaN share %.4f, smallest finite non-zero share %.4f\n", max_nan, min_finite);
+    printf("selftest: mixed 2-byte: smallest mutant difference (elements): toward zero %zu, ties away %zu, subnormals flushed %zu, fused "
+           "%zu; an infinity for a NaN seen in %zu; -0 expected alone / in a group: float16 %zu / %zu, bfloat16 %zu / %zu\n", min_mut[0],
+           min_mut[1], min_mut[2], min_mut[3], upper_half, neg_zero[0][0], neg_zero[0][1], neg_zero[1][0], neg_zero[1][1]);
+    printf("selftest: mixed float32: smallest mutant difference (elements): subnormal product flushed %zu, not scaled %zu; seen in a word "
+           "/ in a 16-byte vector: flushed %zu / %zu, not scaled %zu / %zu, +0 for a -0 product %zu / %zu; signalling NaNs to gather "
+           "%zu / %zu\n", min_flush, min_unscaled, flush_at[0], flush_at[1], unscaled_at[0], unscaled_at[1], zero_at[0], zero_at[1],
+           snan[0], snan[1]);
+    failed += need("a NaN whose upper half reads as an infinity, in a mixed table", upper_half);
+    for (int t = 0; t < 2; t++)
+        failed += need("mixed: -0 in an element that moves alone", neg_zero[t][0]) + need("mixed: -0 in an element of a group", neg_zero[t][1]);
+    for (int w = 0; w < 2; w++)
+        failed += need(w ? "a flushed float32 product in a 16-byte vector" : "a flushed float32 product in a word", flush_at[w]) +
+                  need(w ? "an unscaled float32 element in a 16-byte vector" : "an unscaled float32 element in a word", unscaled_at[w]) +
+                  need(w ? "a float32 -0 product in a 16-byte vector" : "a float32 -0 product in a word", zero_at[w]);
+    return failed;
+}
+
 } // namespace
 
 static int selftest()
@@ -442,6 +681,7 @@ static int selftest()
            S.min_mut[0], S.min_mut[1], S.min_mut[2]);
     printf("selftest: smallest swap difference %zu bytes (FTAR_2INT: largest %zu)\n", S.min_swap, S.max_swap_2int);
     S.failed += movers_selftest();
+    S.failed += mixed_selftest();
     printf("selftest: %d failed\n", S.failed);
     return S.failed ? 1 : 0;
 }

@@ -347,10 +347,11 @@ def test_segment_kernel_on_half_and_pair_types():
 
 def test_gather_movers_on_their_own():
     """gather_check: gather_kernel in both directions through launch_gather, with tables and grids
-    chosen by the checker (tests/kernel_gpu/gen_movers.h) -- element sizes 2, 4, 8, 16; user buffers
-    at every multiple of the type's alignment past a 16-byte boundary (2-byte elements at 0 .. 14,
-    8-byte pairs at 4 and 12, the 16-byte pair at 8), congruent to their packed address or not, and
-    2-byte elements against an odd packed address (units of one byte); entries of one element,
+    chosen by the checker (tests/kernel_gpu/gen_movers.h) -- element sizes 1, 2, 4, 8, 16; user buffers
+    at every multiple of the type's alignment past a 16-byte boundary (1-byte elements at all 16
+    offsets, 2-byte elements at 0 .. 14, 8-byte pairs at 4 and 12, the 16-byte pair at 8), congruent
+    to their packed address or not, 1-byte elements behind a packed start of 3 bytes, and 2-byte
+    elements against an odd packed address (units of one byte); entries of one element,
     around one vector, of 1023 / 1024 / 1025 bytes, around 4 * 64 and 4 * 256 vectors, one tile
     -1 / 0 / +1 element, an entry ending on a tile edge with another behind it, one entry over five
     tiles, 320 one-element entries in one tile (the deal over the four waves), 1024 entries; user
@@ -375,6 +376,33 @@ def test_converting_movers_on_their_own():
     is expected; test_kernel_ref.py shows that a wrong rounding, a fused multiply-convert, a +0 or
     a truncated NaN would each be seen."""
     _run_checker("gather_check", "cvt")
+
+
+def test_mixed_mover_on_its_own():
+    """gather_check mix: gather_mix_kernel in both directions through launch_gather_mix, the type
+    words uploaded behind the table as the product lays them out (ftar::mix_types), on the mixed
+    tables of gen_movers.h -- the converting sizes (1 .. 257 x 8 elements, one tile -1 / 0 / +1, an
+    entry ending on a tile edge, five tiles + 3) with float16, bfloat16 and float32 cycling from
+    each of the three, so every size occurs with every type; user buffers at every multiple of the
+    entry's own alignment, all congruent (float32 in 16-byte vectors, 2-byte entries of class 8) or
+    none (float32 word by word, classes 4, 2, 1); packed starts 0, 4, 8, 12, 20 past a 256-byte
+    boundary (float32 heads of 0, 3, 2, 1 words; whole float32 tiles of 1024 and of 1023 vectors);
+    320 one-element entries with type periods of 3 (every wave meets every type) and 4 (every wave
+    one type); tables of 1024, 1023 and 7 entries (the type array at three offsets); for each of
+    the 6 ordered pairs of types a tile edge exactly between them and one 3 elements in front; two
+    neighbours of one type; pieces of 1020, 1024 and 1028 packed bytes of every type in one tile;
+    pinned tables; the converting tables' pattern, tie and non-finite blocks with float32 entries of
+    1, 5 and 4099 elements between them.  Grids of ntiles, min(7, ntiles) and 1.  Gather (launched
+    with scale 0.5, which must not be applied): every 16-bit pattern widened, float32 words --
+    signalling NaNs among them -- copied bit for bit.  Scatter at the seven scales: a 2-byte entry
+    as in `cvt`; a float32 entry (float)((double)scale * a), ONE multiplication, bit for bit on
+    +-0, subnormal products, products underflowing to -0, the overflow at 3.0000002, infinities and
+    the largest value, any NaN where a NaN is expected.  The whole arena is compared: guards,
+    gaps, packed bytes past the total, the source side.  test_kernel_ref.py counts on the CPU that
+    these tables reach every (type, wave), neighbour pair, edge, threshold, class, head and loop,
+    and that a flushed product, a +0 or an unscaled float32 element would be seen in a word and
+    in a vector."""
+    _run_checker("gather_check", "mix")
 
 
 def test_lds_reduce_on_its_own():

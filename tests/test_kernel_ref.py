@@ -5,7 +5,8 @@ of those matrices' inputs.
 tests/kernel_gpu/ref_check is a host program (no HIP call): `apply` runs the reference over
 operand files, `narrow` its float32 -> 16-bit conversion, `selftest` generates the inputs of every
 GPU case and asserts that they can tell a wrong kernel from a right one (a wrong rounding, flushed
-subnormals, swapped operands, a fused multiply-convert) and that the movers' tables reach what
+subnormals, swapped operands, a fused multiply-convert, a float32 entry of a mixed list not scaled)
+and that the movers' tables -- plain, converting and mixed -- reach what
 they are built to reach (the conditions are listed in ref_check.cpp).  `apply` and `selftest` also
 run in a build with ASan + UBSan.
 
@@ -152,7 +153,17 @@ def test_inputs_tell_a_wrong_kernel_from_a_right_one(ref_check):
     threshold, tile-edge exit and converting class counted non-zero; every converting scatter case
     telling a wrong rounding, flushed subnormals and a fused multiply-convert from the contract;
     -0 and half-infinity NaNs present; the NaN and finite shares; the LDS reduce's operand roles
-    visible in the full tiles and in the ragged rest."""
+    visible in the full tiles and in the ragged rest.  The mixed tables of `gather_check mix`
+    replayed by the entry's own type: for each of float16, bfloat16 and float32 a workgroup's piece,
+    a small piece on each of the four waves, a tile ending inside an entry and at an entry's end
+    with each other type behind it, pieces in a workgroup's later tiles, pieces of 1020 / 1024 /
+    1028 packed bytes; all 9 ordered pairs of neighbouring types in one tile; every converting class
+    per 2-byte type; float32 vector pieces with heads of 1, 2 and 3 words, pieces that are not,
+    the unrolled loop and its remainder, nvec = 1023 and 1024, word loops at 64 and 256 threads; a
+    pinned table and one of 1024 entries.  Per mixed scatter case the converting conditions on the
+    2-byte elements, and on the float32 elements a flushed subnormal product and a missing scale
+    seen; over the matrix both, and a +0 for a -0 product, seen in a word and in a 16-byte vector,
+    and a signalling NaN to gather in both."""
     cp = subprocess.run([ref_check[0], "selftest"], capture_output=True, text=True, timeout=600)
     assert cp.returncode == 0, cp.stdout[-3000:] + cp.stderr[-3000:]
     assert cp.stdout.rstrip().endswith("selftest: 0 failed"), cp.stdout[-3000:]
@@ -162,7 +173,7 @@ def test_inputs_tell_a_wrong_kernel_from_a_right_one(ref_check):
 def test_reference_under_sanitizers(ref_check):
     """The same program built with ASan + UBSan: the reference over operands that reach every
     branch of the rounding (specials against every pattern), and the whole self-test -- the movers'
-    table generators, layouts and replay (gen_movers.h) included."""
+    table generators, layouts and replay (gen_movers.h), those of the mixed tables included."""
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1")
     pat = np.arange(1 << 16, dtype=np.uint16)
     with tempfile.TemporaryDirectory(prefix="ftar_ref_") as tmp:
